@@ -5,21 +5,29 @@ Metric (BASELINE.json): decoded codewords/sec @ 50 iterations, GF(256) 512.256 r
 achieved fraction of the HBM roofline.  A "step" is one pass of the decoder (50 fixed iterations) over one batch
 of codewords whose channel LLRs already sit in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 is launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`: every rank
 decodes its own batch (independent frames, no data-path collective: SURVEY 8e), scaling is weak.
+
+A plain run sets up, warms up, times exactly K steps and prints the result line; `ms_per_step` is the wall time of one timed step.
+--dump-outputs DIR  after the timed steps, rank 0 writes what the last step returned for its batch, as float32 .npy files:
+                decoded.npy [B][N] hard decisions, converged.npy [B] zero-syndrome flags, iterations.npy [B] iterations run.
+                The inputs are seeded, so two runs with the same arguments decode the same codewords.  Above 64 MB in all, a
+                fixed seeded sample of the lanes is written instead, with their indices in lanes.npy.
+--full          also measures, after the timed steps, what the headline does not need: the CPU baselines, other_configs and
+                headline_by_convergence below.
 
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline      dominant kernel (fused EMS iteration): algorithmic bytes per launch / mean launch time (HIP events on
                 the launch stream inside the timed region) against the 8 TB/s HBM peak; `traffic` / `hbm_actual_GBps` = what
                 the kernel really moves (committed PMC passes), `limiter` = what it waits for
-  other_configs (N = 1 only) BASELINE configs 2, 4 and 5 at fixed iterations, one short pass each AFTER the headline's timed region:
+  other_configs (--full, N = 1 only) BASELINE configs 2, 4 and 5 at fixed iterations, one short pass each AFTER the headline's timed region:
                 codewords/s, ms per launch and the fused kernel's algorithmic-bytes roofline (tools/bench_config.py::run_config)
-  cpu_baseline  the compiled reference itself (oracle/_ref, kind "reference") on this host's cores, decode loop only, on a
+  cpu_baseline  (--full) the compiled reference itself (oracle/_ref, kind "reference") on this host's cores, decode loop only, on a
                 bounded sample of the same workload (rank 0, N=1 only); cpu_baseline_port = the oracle's literal restatement
                 on codewords of the same batch (kind "port"; also the fallback when oracle/_ref is absent)
 
-`headline_by_convergence` (rank 0, N = 1): the headline configuration once at 0 dB (no codeword converges: every check on the full
+`headline_by_convergence` (--full, rank 0, N = 1): the headline configuration once at 0 dB (no codeword converges: every check on the full
 path) and once at 2 dB (all converge: exact short lists) -- the kernel's rate depends on how many of the batch's
 codewords are past convergence, and the bench's 1 dB sits between the two.
 """
@@ -37,6 +45,7 @@ for _p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tools")):
 import numpy as np  # noqa: E402
 
 CODE = "divsalar.UNBLDPC.512.256.GF.256"
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes in all
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
@@ -181,6 +190,20 @@ def pmc_traffic(fused, B):
     return None
 
 
+def dump_outputs(path, out, conv, its):
+    """What the timed path returned in its last step (decode_device's three output buffers), as float32 .npy files under `path`.
+    Past DUMP_BYTES a fixed seeded sample of the lanes is written, their indices in lanes.npy."""
+    os.makedirs(path, exist_ok=True)
+    B, N = out.shape
+    arrs = {"decoded": out, "converged": conv, "iterations": its}
+    if 4 * B * (N + 2) + 4096 > DUMP_BYTES:  # (4096: the .npy headers)
+        lanes = np.sort(np.random.default_rng(173).choice(B, (DUMP_BYTES - 4096) // (4 * (N + 2) + 8), replace=False))
+        arrs = {k: v[lanes] for k, v in arrs.items()}
+        np.save(os.path.join(path, "lanes.npy"), lanes.astype(np.float64))
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), v.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -191,14 +214,18 @@ def main():
     ap.add_argument("--nm", type=int, default=32)
     ap.add_argument("--nc", type=int, default=3)
     ap.add_argument("--ebn0", type=float, default=1.0)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="codewords for the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="codewords for the CPU baseline of --full (0 = skip)")
     ap.add_argument("--data", default="harness", choices=["harness", "randn"],
                     help="harness: the reference-compatible link chain generates the codewords and channel LLRs (default); "
                          "randn: all-zero codeword + torch.randn noise")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on a 1-GPU box: every rank uses cuda:0")
-    ap.add_argument("--other-configs", type=int, default=-1, help="1 / 0: also run BASELINE configs 2, 4, 5 after the timed region (default: at N = 1)")
+    ap.add_argument("--other-configs", type=int, default=-1, help="1 / 0: with --full, also run BASELINE configs 2, 4, 5 after the timed region (default: at N = 1)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baselines, other_configs and headline_by_convergence (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0's batch) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import nbldpc_amd as nb
@@ -242,6 +269,8 @@ def main():
 
     # barrier + torch.cuda.synchronize() on both sides, MAX over ranks (nbldpc_amd/ranks.py)
     dt = ranks.timed(rk, timed_step, args.steps, torch.cuda.synchronize)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out.cpu().numpy(), conv.cpu().numpy(), its.cpu().numpy())
     ms_vn, ms_syn, ms_cn, n_cn = timing["vn"], timing["syn"], timing["cn"], timing["n_cn"]
     # whole-job sanity counters: every rank's per-lane (converged, decoded word == transmitted word) flags, gathered in lane order
     lane_flags = torch.stack([conv.to(torch.float64), (out == tx_dev).all(dim=1).to(torch.float64)], dim=1).cpu().numpy()
@@ -287,7 +316,7 @@ def main():
                      "limiter": limiter_text(),
                      "bytes_per_launch": cn_bytes_launch, "ms_per_launch": cn_ms},
     }
-    if rank == 0 and world == 1 and args.cpu_sample != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0:
         threads = os.cpu_count() or 1
         try:
             threads = len(os.sched_getaffinity(0))
@@ -300,7 +329,7 @@ def main():
         res["cpu_baseline"] = ref if ref is not None else port
         res["cpu_baseline_port"] = port
     dec.close()
-    if rank == 0 and world == 1 and args.other_configs != 0:
+    if args.full and rank == 0 and world == 1 and args.other_configs != 0:
         del L, out, conv, its, tx_dev
         torch.cuda.empty_cache()
         res["other_configs"] = other_configs(local_rank)

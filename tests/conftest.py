@@ -1,3 +1,4 @@
+import hashlib
 import json
 import os
 import sys
@@ -22,6 +23,16 @@ def load_golden(name):
     g = np.load(os.path.join(GOLD, name + ".npz"))
     meta = json.loads(str(g["meta"]))
     return g, meta
+
+
+def token_digest(words):
+    """SHA-256 of a whitespace-split text file: equal digests = the same words in the same order."""
+    return hashlib.sha256("\n".join(words).encode()).hexdigest()
+
+
+def value_digest(words):
+    """SHA-256 of the numbers of a whitespace-split text file, labels (words ending in ':') dropped, compared as floats."""
+    return hashlib.sha256(",".join(repr(float(w) + 0.0) for w in words if not w.endswith(":")).encode()).hexdigest()
 
 
 def decoder_kwargs(profile):

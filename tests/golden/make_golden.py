@@ -8,8 +8,10 @@ oracle/ref_driver.cpp, which calls the unmodified CSimulation / CComm / CNBLDPC 
   out/ret/syn_ok [K][B]  CNBLDPC::Decoding output, return value, zero-syndrome check for maxIter = iters[k]
   st_post/st_v2c/st_c2v  message state after state_iters[k] iterations (frame 0; var-major edge order)
 plus FER anchor lines (fer mode).  Large state arrays are subsampled (`state_lanes`) to keep fixtures small.
+`data` writes reference_data.json: digests of the reference's GF-table, code and constellation files, which
+tests/test_host_data.py compares with the files nbldpc_amd/datafiles.py writes.
 
-usage: python tests/golden/make_golden.py [set ...]
+usage: python tests/golden/make_golden.py [set ... | fer:<set> ... | data]
 """
 import json
 import os
@@ -40,6 +42,7 @@ C256_256 = "divsalar.CNBLDPC.256.128.GF.256"
 C128_256 = "divsalar.CNBLDPC.128.64.GF.256"
 C512_256 = "divsalar.CNBLDPC.512.256.GF.256"
 BDS = "BDS.576.288.GF.64"
+GF_TABLES = (4, 8, 16, 32, 64, 128, 256, 512)
 
 # name -> (driver build, profile kwargs, EbN0, frames, iters, state_iters, state_lanes)
 SETS = {
@@ -239,11 +242,29 @@ def run_fer(names):
     json.dump(anchors, open(path, "w"), indent=1)
 
 
+def run_data():
+    sys.path.insert(0, os.path.dirname(HERE))
+    from conftest import token_digest, value_digest
+    import nbldpc_amd.datafiles as df
+    words = lambda f: open(REF + f).read().split()  # noqa: E731
+    tokens = {}
+    for q in GF_TABLES:
+        for stem in ("Arith.Table.GF", "Mat.Repr.GF"):
+            tokens[f"{stem}.{q}.txt"] = token_digest(words(f"{stem}.{q}.txt"))
+    for name in df.codes():
+        tokens[name + ".txt"] = token_digest(words(name + ".txt"))
+    values = {name + ".txt": value_digest(words(name + ".txt")) for name in df.constellations()}
+    json.dump(dict(tokens=tokens, values=values), open(os.path.join(GOLD, "reference_data.json"), "w"), indent=1, sort_keys=True)
+    print(f"data: {len(tokens)} word digests, {len(values)} value digests")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
-    want = sys.argv[1:] or (list(SETS) + list(DEEP_SETS) + ["fer:" + k for k in FER_SETS])
+    want = sys.argv[1:] or (list(SETS) + list(DEEP_SETS) + ["fer:" + k for k in FER_SETS] + ["data"])
     for w in want:
-        if w.startswith("fer:"):
+        if w == "data":
+            run_data()
+        elif w.startswith("fer:"):
             run_fer([w[4:]])
         elif w in DEEP_SETS:
             run_deep(w)
