@@ -10,7 +10,7 @@
  *   int  CNBLDPC::Decoding(double** L_ch, int* DecodeOutput,   nbl_decode_batch()         host buffers
  *        int*, int*)        NBLDPC.h:71, NBLDPC.cpp:607-641    nbl_decode_batch_device()  HBM-resident
  *        -> Decoding_BP :643, Decoding_EMS :778,
- *           Decoding_TEMS :929
+ *           Decoding_TEMS :929, Decoding_BS_TEMS :1145               nbl_create_ex() (method 7)
  *   public members L_post / L_v2c / L_c2v  NBLDPC.h:65-68      nbl_read_state()  (parity tests only)
  *   ~CNBLDPC                                                   nbl_destroy()
  *
@@ -35,11 +35,13 @@ extern "C" {
 #define NBL_METHOD_BP   1 /* exact log-domain QSPA, forward/backward */
 #define NBL_METHOD_EMS  2 /* configuration-set EMS, nm/nc truncated   */
 #define NBL_METHOD_TEMS 4 /* trellis EMS                              */
+#define NBL_METHOD_BS_TEMS 7 /* basic-set trellis EMS: parameters through nbl_create_ex */
 
 typedef enum nbl_status {
 	NBL_OK = 0,
 	NBL_ERR_ARG = -1,        /* bad argument / inconsistent graph (reference: undefined behaviour or exit(-1)) */
-	NBL_ERR_UNSUPPORTED = -2,/* method 3/5/6/7 (reference prints "not developed" and exits, NBLDPC.cpp:618-638) */
+	NBL_ERR_UNSUPPORTED = -2,/* method 3/5/6 (reference prints "not developed" and exits, NBLDPC.cpp:618-638), method 7 without
+	                            nbl_create_ex's parameters, a shape the kernels do not serve                                   */
 	NBL_ERR_NO_DEVICE = -3,  /* no HIP device: there is deliberately no CPU path                               */
 	NBL_ERR_HIP = -4,        /* a HIP runtime call failed                                                      */
 	NBL_ERR_NOMEM = -5
@@ -84,6 +86,21 @@ typedef struct nbl_decoder nbl_decoder;
  * with a message, at creation, never at the first decode. */
 nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                       const nbl_params *params, int device, nbl_decoder **out);
+
+/* Parameters of the methods nbl_params does not carry: basic-set T-EMS (NBL_METHOD_BS_TEMS), the fields CNBLDPC::Initial copies
+ * for method 7 (NBLDPC.cpp:332-337; profile lines "BSTEMS Nm / Nc / Factor / Offset").
+ *   bs_nm      elements of the basic set, 1 <= bs_nm <= q - 1 (NBL_ERR_ARG otherwise: the reference reads past its arrays), and
+ *              at most 16 (NBL_ERR_UNSUPPORTED above: the kernel enumerates the configurations as masks of bs_nm bits)
+ *   bs_nc      largest number of deviating columns of a configuration, >= 0
+ *   bs_factor  c2v scaling (divisor, != 0), bs_offset its dead zone, as ems_/tems_factor and _offset */
+typedef struct nbl_params_ext {
+	int32_t bs_nm, bs_nc;
+	double  bs_factor, bs_offset;
+} nbl_params_ext;
+/* nbl_create with the extension parameters; ext may be NULL (then it IS nbl_create, and method 7 is NBL_ERR_UNSUPPORTED).
+ * ext is read for method 7 only. */
+nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
+                         const nbl_params *params, const nbl_params_ext *ext, int device, nbl_decoder **out);
 void nbl_destroy(nbl_decoder *dec);
 
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).

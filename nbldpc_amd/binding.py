@@ -13,10 +13,10 @@ from . import datafiles
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBL_HIP_LIB") or os.path.join(_HERE, "csrc", "libnbldpc_hip.so")  # NBL_HIP_LIB: A/B builds
 
-METHOD_BP, METHOD_EMS, METHOD_TEMS = 1, 2, 4
+METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_BS_TEMS = 1, 2, 4, 7
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
            "nbl_workspace_bytes")
@@ -41,6 +41,10 @@ class Params(C.Structure):
                 ("poll_every", C.c_int32), ("max_batch", C.c_int32)]
 
 
+class ParamsExt(C.Structure):
+    _fields_ = [("bs_nm", C.c_int32), ("bs_nc", C.c_int32), ("bs_factor", C.c_double), ("bs_offset", C.c_double)]
+
+
 _lib = None
 
 
@@ -62,6 +66,9 @@ def load_library():
         L.nbl_abi_version.restype = C.c_int32
         L.nbl_create.restype = C.c_int
         L.nbl_create.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_create_ex.restype = C.c_int
+        L.nbl_create_ex.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(ParamsExt), C.c_int,
+                                    C.POINTER(C.c_void_p)]
         L.nbl_destroy.argtypes = [C.c_void_p]
         L.nbl_destroy.restype = None
         L.nbl_decode_batch.restype = C.c_int
@@ -102,10 +109,12 @@ class Code:
 
 
 class Decoder:
-    """Batched decoder handle (nbl_create .. nbl_destroy)."""
+    """Batched decoder handle (nbl_create .. nbl_destroy).  Basic-set T-EMS (method 7) takes bs_nm / bs_nc / bs_factor / bs_offset
+    through nbl_create_ex; without bs_nm the handle is made by nbl_create, which refuses method 7."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
-                 tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None):
+                 tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
+                 bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -115,7 +124,12 @@ class Decoder:
                              tems_offset, fixed_iters, poll_every, max_batch)
         desc = code.desc()
         h = C.c_void_p()
-        rc = self.lib.nbl_create(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), device, C.byref(h))
+        if bs_nm is None:
+            rc = self.lib.nbl_create(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), device, C.byref(h))
+        else:
+            self.ext = ParamsExt(bs_nm, bs_nc, bs_factor, bs_offset)
+            rc = self.lib.nbl_create_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params),
+                                        C.byref(self.ext), device, C.byref(h))
         if rc != 0:
             raise NblError(rc, self.lib.nbl_last_error(None).decode())
         self.h = h

@@ -1,7 +1,7 @@
 // nbldpc_amd/csrc/nbl_api.cpp -- C ABI (include/nbldpc.h) on top of the HIP kernels.
 //
 // Replaces CNBLDPC::Initial's decoder set-up (NBLDPC.cpp:140-377: graph cross indices, message buffers) and
-// CNBLDPC::Decoding's iteration loop (NBLDPC.cpp:607-641 -> Decoding_BP/EMS/TEMS) for a batch of codewords.
+// CNBLDPC::Decoding's iteration loop (NBLDPC.cpp:607-641 -> Decoding_BP/EMS/TEMS/BS_TEMS) for a batch of codewords.
 // No CPU decode path exists in this library: without a HIP device nbl_create() fails.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -20,6 +20,7 @@ static thread_local std::string g_create_error;
 struct nbl_decoder {
 	int device = -1;
 	nbl_params prm{};
+	nbl_params_ext ext{};       // method 7 only (nbl_create_ex)
 	NblGraphDev g{};
 	NblWork w{};
 	std::vector<void *> graph_allocs;
@@ -232,6 +233,12 @@ static nbl_status fail_create(nbl_decoder *d, nbl_status st, const std::string &
 extern "C" nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                                  const nbl_params *params, int device, nbl_decoder **out)
 {
+	return nbl_create_ex(code, gf_mul, gf_inv, params, nullptr, device, out);
+}
+
+extern "C" nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
+                                    const nbl_params *params, const nbl_params_ext *ext, int device, nbl_decoder **out)
+{
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
 	if (!code || !gf_mul || !gf_inv || !params) return fail_create(nullptr, NBL_ERR_ARG, "null argument");
@@ -241,7 +248,10 @@ extern "C" nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_m
 	if (q > 256) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "fields above GF(256) are not supported (one wave holds at most 4 symbols per lane)");
 	switch (params->method) {
 	case NBL_METHOD_EMS: case NBL_METHOD_BP: case NBL_METHOD_TEMS: break;
-	default: return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "decode method not supported (reference: 'has not been developed' / OSD / BS-TEMS)");
+	case NBL_METHOD_BS_TEMS:
+		if (!ext) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "BS-TEMS (method 7): its parameters (bs_nm, bs_nc, bs_factor, bs_offset) go through nbl_create_ex");
+		break;
+	default: return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "decode method not supported (reference: 'has not been developed' / OSD)");
 	}
 	if (params->max_iter < 0) return fail_create(nullptr, NBL_ERR_ARG, "max_iter < 0");
 	if (params->method == NBL_METHOD_EMS) {
@@ -251,6 +261,14 @@ extern "C" nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_m
 	}
 	if (params->method == NBL_METHOD_TEMS && (params->tems_nr < 1 || params->tems_nc < 0))
 		return fail_create(nullptr, NBL_ERR_ARG, "tems_nr < 1 or tems_nc < 0");
+	if (params->method == NBL_METHOD_BS_TEMS) {
+		// the reference's basic-set arrays hold q elements (NBLDPC.cpp:333): bs_nm >= q reads past them
+		if (ext->bs_nm < 1 || ext->bs_nm >= q) return fail_create(nullptr, NBL_ERR_ARG, "BS-TEMS: bs_nm must be at least 1 and below q");
+		if (ext->bs_nc < 0) return fail_create(nullptr, NBL_ERR_ARG, "BS-TEMS: bs_nc < 0");
+		if (!(ext->bs_factor != 0.0)) return fail_create(nullptr, NBL_ERR_ARG, "BS-TEMS: bs_factor must be non-zero (c2v values are divided by it)");
+		if (ext->bs_nm > 16)
+			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "BS-TEMS: bs_nm above 16 is not supported (the kernel enumerates configurations as bs_nm-bit masks)");
+	}
 
 	// ---- host-side graph indices (NBLDPC.cpp:236-263) -------------------------------------------------------
 	std::vector<int> voff(N + 1, 0), coff(M + 1, 0);
@@ -318,6 +336,7 @@ extern "C" nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_m
 	nbl_decoder *d = new nbl_decoder();
 	d->device = device;
 	d->prm = *params;
+	if (params->method == NBL_METHOD_BS_TEMS) d->ext = *ext;
 	if (hipSetDevice(device) != hipSuccess) return fail_create(d, NBL_ERR_HIP, "hipSetDevice failed");
 	if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) return fail_create(d, NBL_ERR_HIP, "hipStreamCreate failed");
 	if (const char *e = getenv("NBL_GRAPH")) d->use_graph = atoi(e) != 0;
@@ -497,6 +516,7 @@ static nbl_status launch_cn(nbl_decoder *d, const NblRun &r, hipStream_t st)
 		else if (d->force_generic != 1 && small_on) HIP_TRY(d, nbl_launch_cn_bp_small(d->g, d->w, r, false, st));
 		else HIP_TRY(d, nbl_launch_cn_bp(d->g, d->w, r, st));
 		break;
+	case NBL_METHOD_BS_TEMS: HIP_TRY(d, nbl_launch_cn_bstems(d->g, d->w, r, st)); break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
 	return NBL_OK;
@@ -614,8 +634,9 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 	r.B = B;
 	r.fixed_iters = p.fixed_iters;
 	if (p.method == NBL_METHOD_EMS) { r.nm = p.ems_nm; r.nc = p.ems_nc; r.factor = p.ems_factor; r.offset = p.ems_offset; }
+	else if (p.method == NBL_METHOD_BS_TEMS) { r.nm = d->ext.bs_nm; r.nc = d->ext.bs_nc; r.factor = d->ext.bs_factor; r.offset = d->ext.bs_offset; }
 	else { r.nr = p.tems_nr; r.nc = p.tems_nc; r.factor = p.tems_factor; r.offset = p.tems_offset; }
-	r.damp_old = (p.method == NBL_METHOD_BP) ? 0.5 : 0.25;  // NBLDPC.cpp:739 / :1046
+	r.damp_old = (p.method == NBL_METHOD_BP) ? 0.5 : 0.25;  // NBLDPC.cpp:739 / :1046 / :1262
 	r.damp_new = (p.method == NBL_METHOD_BP) ? 0.5 : 0.75;
 	d->launches[0] = d->launches[1] = d->launches[2] = 0;
 	c.fused = fused_shape(d) && d->force_generic == 0 && d->c2v_alt;

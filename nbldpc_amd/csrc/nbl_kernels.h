@@ -37,6 +37,11 @@ hipError_t nbl_launch_cn_tems64(const NblGraphDev &g, const NblWork &w, const Nb
 bool nbl_tems256_applicable(const NblGraphDev &g, bool all_dc4, int nr, int nc);
 hipError_t nbl_launch_cn_tems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
+// basic-set T-EMS check node, any q = 4 .. 256, check degree <= 8, 1 <= nm <= min(q - 1, 16) (nbl_cn_bstems.hip)
+bool nbl_bstems_applicable(const NblGraphDev &g, int nm, int nc);
+size_t nbl_bstems_lds_bytes(const NblGraphDev &g);
+hipError_t nbl_launch_cn_bstems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+
 // log-QSPA check node for GF(256), check degree 4 (nbl_cn_bp256.hip)
 bool nbl_bp256_applicable(const NblGraphDev &g, bool all_dc4);
 hipError_t nbl_launch_cn_bp256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);

@@ -62,7 +62,9 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	p.poll_every = fixed_iters ? 0 : 2;
 	p.max_batch = 0; // the workspace is sized at the first DecodingBatch call
 	if (dec) { nbl_destroy(dec); dec = nullptr; }
-	nbl_status st = nbl_create(&code, mul.data(), inv.data(), &p, device, &dec);
+	// basic-set T-EMS: its parameters go through the extension struct (NBLDPC.cpp:332-337)
+	nbl_params_ext ext = {sim.bs_tems_nm, sim.bs_tems_nc, sim.bs_tems_factor, sim.bs_tems_offset};
+	nbl_status st = nbl_create_ex(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr, device, &dec);
 	if (st != NBL_OK) {
 		error = nbl_last_error(nullptr);
 		std::cerr << error << std::endl; // the reference prints and exits for its own configuration errors (NBLDPC.cpp:284-285)

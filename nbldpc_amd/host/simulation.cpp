@@ -102,6 +102,9 @@ int CSimulation::Show(int mode)
 			cout << "Algorithm: EMS\tNm: " << ems_nm << "\tNc: " << ems_nc << "\tFactor: " << ems_factor << "\tOffset: " << ems_offset << endl;
 		else if (decodeMethod == T_EMS_DECODE)
 			cout << "Algorithm: Trellis EMS\tNr: " << tems_nr << "\tNc: " << tems_nc << "\tFactor: " << tems_factor << "\tOffset: " << tems_offset << endl;
+		else if (decodeMethod == BS_TEMS_DECODE)
+			cout << "Algorithm: BS_TEMS_DECODE\tBS_TEMS_Nm: " << bs_tems_nm << "\tBS_TEMS_Nc: " << bs_tems_nc << "\tFactor: " << bs_tems_factor
+			     << "\tOffset: " << bs_tems_offset << endl;
 		else cout << "Algorithm: method " << decodeMethod << " (not available on this decode path)" << endl;
 		cout << "Modulation: " << nQAM << "-QAM" << "\tConf: " << ConstellationFileName << endl;
 		cout << "SNR: " << snrBegin << ":" << snrStep << ":" << snrStop << (randomMsg ? "\tRandom Sequence\n" : "\tALL 0 sequence\n")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the other BASELINE.json configurations (parity-test cases, not the headline bench line).
 
-usage: python tools/bench_config.py cfg1|cfg2|cfg3|cfg3nc2|cfg3nm24|cfg3nm48|cfg3nm64|cfg4|cfg5|tems256|ems64|bp64|ems16|tems16|bp16 [batch] [steps] [ebn0]
+usage: python tools/bench_config.py cfg1|cfg2|cfg3|cfg3nc2|cfg3nm24|cfg3nm48|cfg3nm64|cfg4|cfg5|tems256|ems64|bp64|ems16|tems16|bp16|bstems16|bstems256 [batch] [steps] [ebn0]
 Prints one JSON line: codewords/s at fixed iterations with HBM-resident inputs, plus the algorithmic-bytes roofline fraction
 (8(q-1)[N + I(N + 4E + D E)] + 4N + 4 bytes per codeword, D = 1 for BP / T-EMS).
 """
@@ -32,6 +32,9 @@ CFG = {
     "ems16": dict(code="divsalar.UNBLDPC.512.256.GF.16", method=nb.METHOD_EMS, iters=50, batch=8192, kw=dict(ems_nm=8, ems_nc=3), D=0, ebn0=2.0, mod="bpsk"),
     "tems16": dict(code="divsalar.UNBLDPC.512.256.GF.16", method=nb.METHOD_TEMS, iters=50, batch=8192, kw=dict(tems_nr=2, tems_nc=3), D=1, ebn0=2.0, mod="bpsk"),
     "bp16": dict(code="divsalar.UNBLDPC.512.256.GF.16", method=nb.METHOD_BP, iters=50, batch=8192, kw=dict(), D=1, ebn0=2.0, mod="bpsk"),
+    # basic-set T-EMS (method 7): one check per wave, unfused iteration
+    "bstems16": dict(code="divsalar.UNBLDPC.512.256.GF.16", method=nb.METHOD_BS_TEMS, iters=50, batch=8192, kw=dict(bs_nm=4, bs_nc=2), D=1, ebn0=2.0, mod="bpsk"),
+    "bstems256": dict(code="divsalar.UNBLDPC.512.256.GF.256", method=nb.METHOD_BS_TEMS, iters=50, batch=2048, kw=dict(bs_nm=8, bs_nc=3), D=1, ebn0=1.5, mod="bpsk"),
     "cfg5": dict(code="divsalar.CNBLDPC.512.256.GF.256", method=nb.METHOD_BP, iters=100, batch=1024, kw=dict(), D=1, ebn0=10.0, mod="qam"),
 }
 
