@@ -35,13 +35,15 @@ extern "C" {
 #define NBL_METHOD_BP   1 /* exact log-domain QSPA, forward/backward */
 #define NBL_METHOD_EMS  2 /* configuration-set EMS, nm/nc truncated   */
 #define NBL_METHOD_TEMS 4 /* trellis EMS                              */
+#define NBL_METHOD_OSD  6 /* ordered-statistics decoding alone, no iterations: through nbl_create_osd */
 #define NBL_METHOD_BS_TEMS 7 /* basic-set trellis EMS: parameters through nbl_create_ex */
 
 typedef enum nbl_status {
 	NBL_OK = 0,
 	NBL_ERR_ARG = -1,        /* bad argument / inconsistent graph (reference: undefined behaviour or exit(-1)) */
-	NBL_ERR_UNSUPPORTED = -2,/* method 3/5/6 (reference prints "not developed" and exits, NBLDPC.cpp:618-638), method 7 without
-	                            nbl_create_ex's parameters, a shape the kernels do not serve                                   */
+	NBL_ERR_UNSUPPORTED = -2,/* method 3/5 (reference prints "not developed" and exits, NBLDPC.cpp:618-638), method 6 without
+	                            nbl_create_osd's parameters, method 7 without nbl_create_ex's, a shape the kernels do not serve,
+	                            an OSD matrix that is too large or not of full row rank                                        */
 	NBL_ERR_NO_DEVICE = -3,  /* no HIP device: there is deliberately no CPU path                               */
 	NBL_ERR_HIP = -4,        /* a HIP runtime call failed                                                      */
 	NBL_ERR_NOMEM = -5
@@ -101,6 +103,39 @@ typedef struct nbl_params_ext {
  * ext is read for method 7 only. */
 nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                          const nbl_params *params, const nbl_params_ext *ext, int device, nbl_decoder **out);
+
+/* Ordered-statistics decoding (OSD.h): post-processing of the frames an iterative method leaves unconverged (order >= 0, methods
+ * 1/2/4/7, NBLDPC.cpp:769-775 and its twins), or the whole decode (NBL_METHOD_OSD: Decoding_OSD_bit(L_ch, .., flag = 1), order 0
+ * when order < 0, flag taken as 1, converged = 0 and iters = 0 on return).  Post-processing changes only out_sym of the codewords
+ * that did not converge; converged, iters and the message state stay as the iterations left them (the reference, too, returns
+ * "not converged" after OSD).  With max_iter = 0 the reference never runs the post-processing, and neither does this.
+ *   order     sim.OSD_order: -1 = off (methods 1/2/4/7); 0 .. 3; above 3 behaves as 3 (OSD.h:139-165 are ">=" tests)
+ *   flag      sim.OSD_flag: 1 = reliabilities and base word from L_ch; 0 = from the factor-weighted sum of the posteriors of every
+ *             iteration (NBLDPC.cpp:687) and the last iteration's decisions
+ *   factor    sim.OSD_factor (alpha), read by flag 0 only
+ *   crc_len   sim.crcLen; crc_rows sim.crc_correctLen: CRC rows put above the binary parity-check matrix (OSD.h:37-48, 472-509);
+ *             crc_rows > 0 needs crc_len 8, 16 or 24 (NBL_ERR_ARG otherwise: the reference's generator is empty and its
+ *             elimination never ends)
+ *   gf_mat    [q][p][p] bytes, gf_mat[e][l][k] = GFElement[e].ValueMatric[l][k]: the binary image of "multiply by e" as the caller's
+ *             loader left it.  The reference's loader (GF.cpp:137) reads q-2 of the q-1 matrices, so alpha^(q-2)'s stays zero; pass
+ *             the same to reproduce it, or the full set for the true binary image.
+ * The binary matrix [crc_rows; H_bit] ((crc_rows + M p) rows of N p bits, q = 2^p) is built and checked once, at creation, before
+ * any device call: N p above NBL_OSD_MAX_BITS (the matrix and the candidate codewords live in one workgroup's LDS; every shipped
+ * code fits) and a matrix without full row rank (the reference's elimination never ends on one) are NBL_ERR_UNSUPPORTED.
+ * Known deviation: positions of equal reliability are ordered by index (the reference's std::sort is not stable); this only
+ * matters for exact ties, e.g. the all-zero LLRs of punctured symbols under flag 1.
+ * osd == NULL: this is nbl_create_ex (and method 6 is NBL_ERR_UNSUPPORTED). */
+#define NBL_OSD_MAX_BITS 1024
+typedef struct nbl_osd_params {
+	int32_t order;
+	int32_t flag;
+	double  factor;
+	int32_t crc_len;
+	int32_t crc_rows;
+	const uint8_t *gf_mat;
+} nbl_osd_params;
+nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                          const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out);
 void nbl_destroy(nbl_decoder *dec);
 
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).

@@ -13,10 +13,10 @@ from . import datafiles
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBL_HIP_LIB") or os.path.join(_HERE, "csrc", "libnbldpc_hip.so")  # NBL_HIP_LIB: A/B builds
 
-METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_BS_TEMS = 1, 2, 4, 7
+METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
            "nbl_workspace_bytes")
@@ -45,6 +45,11 @@ class ParamsExt(C.Structure):
     _fields_ = [("bs_nm", C.c_int32), ("bs_nc", C.c_int32), ("bs_factor", C.c_double), ("bs_offset", C.c_double)]
 
 
+class OsdParams(C.Structure):
+    _fields_ = [("order", C.c_int32), ("flag", C.c_int32), ("factor", C.c_double), ("crc_len", C.c_int32), ("crc_rows", C.c_int32),
+                ("gf_mat", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -69,6 +74,9 @@ def load_library():
         L.nbl_create_ex.restype = C.c_int
         L.nbl_create_ex.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(ParamsExt), C.c_int,
                                     C.POINTER(C.c_void_p)]
+        L.nbl_create_osd.restype = C.c_int
+        L.nbl_create_osd.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(ParamsExt),
+                                     C.POINTER(OsdParams), C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_destroy.argtypes = [C.c_void_p]
         L.nbl_destroy.restype = None
         L.nbl_decode_batch.restype = C.c_int
@@ -110,11 +118,15 @@ class Code:
 
 class Decoder:
     """Batched decoder handle (nbl_create .. nbl_destroy).  Basic-set T-EMS (method 7) takes bs_nm / bs_nc / bs_factor / bs_offset
-    through nbl_create_ex; without bs_nm the handle is made by nbl_create, which refuses method 7."""
+    through nbl_create_ex; without bs_nm the handle is made by nbl_create, which refuses method 7.  OSD (method 6, or post-processing
+    of methods 1/2/4/7 with osd_order >= 0) takes osd_* / crc_len / crc_rows / gf_mat through nbl_create_osd; with osd_order=None the
+    handle is made as before, so method 6 is refused.  gf_mat=None: the GF element matrices as the reference's loader leaves them
+    (datafiles.gf_matrices(q, as_loaded=True))."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
-                 bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0):
+                 bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
+                 gf_mat=None):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -124,7 +136,13 @@ class Decoder:
                              tems_offset, fixed_iters, poll_every, max_batch)
         desc = code.desc()
         h = C.c_void_p()
-        if bs_nm is None:
+        if osd_order is not None:
+            self._gf_mat = np.ascontiguousarray(datafiles.gf_matrices(code.q) if gf_mat is None else gf_mat, dtype=np.uint8)
+            self.osd = OsdParams(osd_order, osd_flag, osd_factor, crc_len, crc_rows, self._gf_mat.ctypes.data)
+            self.ext = ParamsExt(bs_nm, bs_nc, bs_factor, bs_offset) if bs_nm is not None else None
+            rc = self.lib.nbl_create_osd(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params),
+                                         C.byref(self.ext) if self.ext is not None else None, C.byref(self.osd), device, C.byref(h))
+        elif bs_nm is None:
             rc = self.lib.nbl_create(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), device, C.byref(h))
         else:
             self.ext = ParamsExt(bs_nm, bs_nc, bs_factor, bs_offset)
@@ -218,6 +236,13 @@ class Decoder:
         self.lib.nbl_debug_channel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
         self._chk(self.lib.nbl_debug_channel(self.h, tx_index.ctypes.data, lane_state.ctypes.data, sigma, B, rx.ctypes.data, C.byref(frac)))
         return rx, frac.value
+
+    def debug_osd_sums(self, b):
+        """diagnostic: the flag-0 posterior sums S [N][p] of codeword b after the last decode"""
+        S = np.zeros((self.code.N, self.code.q.bit_length() - 1))
+        self.lib.nbl_debug_osd_sums.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        self._chk(self.lib.nbl_debug_osd_sums(self.h, b, S.ctypes.data))
+        return S
 
     def read_lch(self, b):
         L = np.zeros((self.code.N, self.code.q - 1))

@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../include/nbldpc.h"
 #include "nbl_kernels.h"
+#include "nbl_osd.h"
 
 static thread_local std::string g_create_error;
 
@@ -21,6 +22,11 @@ struct nbl_decoder {
 	int device = -1;
 	nbl_params prm{};
 	nbl_params_ext ext{};       // method 7 only (nbl_create_ex)
+	bool osd_on = false;        // OSD stage after the iterations (method 6, or order >= 0; nbl_create_osd)
+	bool osd_acc = false;       // flag-0 posterior sums after every variable-node pass (needs w.post)
+	NblOsdDev osd{};            // H uploaded at creation; S set per decode
+	double osd_factor = 0.0;
+	double *osd_S = nullptr;    // [cap][N p]
 	NblGraphDev g{};
 	NblWork w{};
 	std::vector<void *> graph_allocs;
@@ -67,7 +73,7 @@ struct nbl_decoder {
 	// hipGraph replay of the iteration loop: one executable graph per window of iterations (fixed iterations: the whole loop;
 	// early exit: the `poll_every` iterations between two polls), captured on the decoder's own stream the first time a window is
 	// run with a given set of buffers, replayed on the caller's stream afterwards.  NBL_GRAPH=0 switches it off.
-	struct GraphKey { const void *lin, *lch, *v2c, *c2v, *alt, *post; int B, record, generic, fused; };
+	struct GraphKey { const void *lin, *lch, *v2c, *c2v, *alt, *post, *osd_s; int B, record, generic, fused; };
 	GraphKey gkey{};
 	std::vector<hipGraphExec_t> gexec; // index = window number
 	int *d_active = nullptr;           // [cap] active list (early exit, batches of NBL_COMPACT_MIN codewords or more)
@@ -123,7 +129,8 @@ static void drop_graphs(nbl_decoder *d)
 static void free_workspace(nbl_decoder *d)
 {
 	drop_graphs(d);
-	void *ptrs[] = {d->w.Lch, d->w.v2c, d->w.c2v, d->w.post, d->w.dec, d->w.out, d->w.iters, d->w.done, d->d_Lin, d->d_conv8, d->c2v_alt, d->w.edge_dec, d->d_active, d->c2v_zero};
+	void *ptrs[] = {d->w.Lch, d->w.v2c, d->w.c2v, d->w.post, d->w.dec, d->w.out, d->w.iters, d->w.done, d->d_Lin, d->d_conv8, d->c2v_alt, d->w.edge_dec, d->d_active, d->c2v_zero, d->osd_S};
+	d->osd_S = nullptr;
 	d->c2v_zero = nullptr;
 	d->d_active = nullptr;
 	d->w.active = nullptr;
@@ -183,7 +190,8 @@ static nbl_status ensure_workspace(nbl_decoder *d, int B)
 	// v2c only exists in HBM when something reads it: the unfused path, or state read-back
 	// (damped methods always keep it: the damping reads the previous iteration's v2c)
 	const bool want_v2c = d->prm.method != NBL_METHOD_EMS || !fused_shape(d) || d->record_state || d->force_generic != 0;
-	if (B <= d->cap && (!d->record_state || d->w.post) && (!want_v2c || d->w.v2c)) return NBL_OK;
+	const bool want_post = d->record_state || d->osd_acc;
+	if (B <= d->cap && (!want_post || d->w.post) && (!want_v2c || d->w.v2c)) return NBL_OK;
 	int cap = B > d->cap ? B : d->cap;
 	free_workspace(d);
 	const size_t q = d->g.q, N = d->g.N, E = d->g.E;
@@ -197,7 +205,8 @@ static nbl_status ensure_workspace(nbl_decoder *d, int B)
 		HIP_TRY(d, alloc((void **)&d->c2v_zero, E * q * 8)); // one block for every codeword (NblWork::c2v_prev_shared)
 		HIP_TRY(d, hipMemset(d->c2v_zero, 0, E * q * 8));
 	}
-	if (d->record_state) HIP_TRY(d, alloc((void **)&d->w.post, (size_t)cap * N * q * 8));
+	if (want_post) HIP_TRY(d, alloc((void **)&d->w.post, (size_t)cap * N * q * 8));
+	if (d->osd_acc) HIP_TRY(d, alloc((void **)&d->osd_S, (size_t)cap * N * d->g.p * 8));
 	HIP_TRY(d, alloc((void **)&d->w.dec, (size_t)cap * N * 4));
 	if (d->prm.method != NBL_METHOD_EMS) HIP_TRY(d, alloc((void **)&d->w.edge_dec, (size_t)cap * E * 4));
 	HIP_TRY(d, alloc((void **)&d->w.out, (size_t)cap * N * 4));
@@ -239,6 +248,96 @@ extern "C" nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_m
 extern "C" nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                                     const nbl_params *params, const nbl_params_ext *ext, int device, nbl_decoder **out)
 {
+	return nbl_create_osd(code, gf_mul, gf_inv, params, ext, nullptr, device, out);
+}
+
+// G_GaussEliminate_bit (OSD.h:258-324), literally: forward elimination with the pivot repair from the rows below and the rotation of
+// order[row..] when no row has the bit
+static void g_gauss_eliminate(std::vector<std::vector<uint8_t>> &m, int col_length, int row_length, std::vector<int> &order)
+{
+	for (int row = 0; row < row_length; row++) {
+		int col = order[row];
+		if (m[row][col] == 0) {
+			bool exchanged = false;
+			for (int up = row + 1; up < row_length; up++)
+				if (m[up][col] != 0) {
+					for (int i = 0; i < col_length; i++) m[row][i] ^= m[up][i];
+					exchanged = true;
+					break;
+				}
+			if (!exchanged) {
+				const int flag = row;
+				row--;
+				for (int i = flag; i < col_length - 1; i++) std::swap(order[i], order[i + 1]);
+			}
+		}
+		for (int up = row + 1; up < row_length; up++)
+			if (m[up][col] != 0)
+				for (int i = 0; i < col_length; i++) m[up][i] ^= m[row][i];
+	}
+	for (int row = row_length - 1; row > 0; row--)
+		for (int up = row - 1; up >= 0; up--)
+			if (m[up][order[row]] == 1)
+				for (int i = 0; i < col_length; i++) m[up][i] ^= m[row][i];
+}
+
+// [CRC rows; H_bit] of Decoding_OSD_bit (OSD.h:44-57): H_bit as CNBLDPC::Initial builds it (NBLDPC.cpp:416-430, plain assignment in
+// variable-major edge order), the CRC rows as CRCMatrixGen (OSD.h:472-509).  Returns the rows, or an error text.
+static std::string osd_matrix(const nbl_code_desc *code, int p, const nbl_osd_params *o, std::vector<std::vector<uint8_t>> &rows)
+{
+	const int N = code->N, M = code->M, n = N * p, Mb = M * p, msg = n - Mb, L = o->crc_len, cr = o->crc_rows;
+	std::vector<std::vector<uint8_t>> H((size_t)Mb, std::vector<uint8_t>(n, 0));
+	for (int v = 0, e = 0; v < N; v++)
+		for (int j = 0; j < code->var_deg[v]; j++, e++) {
+			const int chk = code->var_chk[e], h = code->var_h[e];
+			for (int k = 0; k < p; k++)
+				for (int l = 0; l < p; l++) H[(size_t)p * chk + k][(size_t)p * v + l] = o->gf_mat[((size_t)h * p + l) * p + k];
+		}
+	rows.clear();
+	if (cr > 0) {
+		if (msg - L <= 0) return "OSD: the CRC generator has no rows (crc_len >= N p - M p)";
+		std::vector<std::vector<uint8_t>> G((size_t)(msg - L), std::vector<uint8_t>(msg, 0));
+		static const int taps8[] = {0, 1, 4, 5, 7, 8}, taps16[] = {0, 4, 11, 16}, taps24[] = {0, 1, 18, 19, 23, 24};
+		const int *taps = L == 8 ? taps8 : L == 16 ? taps16 : taps24;
+		const int ntaps = L == 16 ? 4 : 6;
+		for (int i = 0; i < msg - L; i++)
+			for (int t = 0; t < ntaps; t++) G[i][i + taps[t]] = 1;
+		std::vector<int> seri(msg);
+		for (int i = 0; i < msg; i++) seri[i] = i;
+		g_gauss_eliminate(G, msg, msg - L, seri);
+		for (int i = 0; i < cr; i++) {
+			std::vector<uint8_t> r(n, 0);
+			r[i + msg - cr] = 1;
+			for (int j = 0; j < msg - L; j++) r[j] = G[j][msg - cr + i];
+			rows.push_back(r);
+		}
+	}
+	for (auto &r : H) rows.push_back(r);
+	return "";
+}
+
+// GF(2) rank of a row set (column order does not matter)
+static int gf2_rank(std::vector<std::vector<uint64_t>> m, int nw)
+{
+	int rank = 0;
+	const int R = (int)m.size();
+	for (int c = 0; c < nw * 64 && rank < R; c++) {
+		int piv = -1;
+		for (int r = rank; r < R; r++)
+			if ((m[r][c >> 6] >> (c & 63)) & 1) { piv = r; break; }
+		if (piv < 0) continue;
+		std::swap(m[piv], m[rank]);
+		for (int r = 0; r < R; r++)
+			if (r != rank && ((m[r][c >> 6] >> (c & 63)) & 1))
+				for (int x = 0; x < nw; x++) m[r][x] ^= m[rank][x];
+		rank++;
+	}
+	return rank;
+}
+
+extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                     const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
+{
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
 	if (!code || !gf_mul || !gf_inv || !params) return fail_create(nullptr, NBL_ERR_ARG, "null argument");
@@ -251,7 +350,46 @@ extern "C" nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *g
 	case NBL_METHOD_BS_TEMS:
 		if (!ext) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "BS-TEMS (method 7): its parameters (bs_nm, bs_nc, bs_factor, bs_offset) go through nbl_create_ex");
 		break;
-	default: return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "decode method not supported (reference: 'has not been developed' / OSD)");
+	case NBL_METHOD_OSD:
+		if (!osd) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "OSD (method 6): its parameters (order, flag, factor, crc_len, crc_rows, gf_mat) go through nbl_create_osd");
+		break;
+	default: return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "decode method not supported (reference: 'has not been developed')");
+	}
+	// ---- OSD parameters and the binary matrix, before any device call ----
+	const bool osd_on = osd && (params->method == NBL_METHOD_OSD || osd->order >= 0);
+	std::vector<uint64_t> osd_words;
+	int osd_R = 0;
+	if (osd) {
+		if (osd->order < -1) return fail_create(nullptr, NBL_ERR_ARG, "OSD: order < -1");
+		if (osd->flag != 0 && osd->flag != 1) return fail_create(nullptr, NBL_ERR_ARG, "OSD: flag must be 0 or 1");
+		if (!osd->gf_mat) return fail_create(nullptr, NBL_ERR_ARG, "OSD: gf_mat is NULL");
+		if (osd->crc_rows < 0 || osd->crc_rows > osd->crc_len) return fail_create(nullptr, NBL_ERR_ARG, "OSD: crc_rows must be in 0 .. crc_len");
+		if (osd->crc_rows > 0 && osd->crc_len != 8 && osd->crc_len != 16 && osd->crc_len != 24)
+			return fail_create(nullptr, NBL_ERR_ARG, "OSD: CRC rows need crc_len 8, 16 or 24 (the reference's CRC generator is empty otherwise and its elimination never ends)");
+	}
+	if (osd_on) {
+		const int p = ilog2(q), n = N * p;
+		// (every n up to the cap fits: nbl_osd_lds_bytes(1024, .) = 160,464 B of the 163,840 B of one workgroup; checked here, before any
+		// device call, so that a change of either limit cannot reach the first decode)
+		if (n > NBL_OSD_MAX_BITS || nbl_osd_lds_bytes(n, 0) > NBL_OSD_MAX_LDS)
+			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "OSD: N log2(q) above NBL_OSD_MAX_BITS (1024) does not fit the kernel's LDS");
+		for (int v = 0, e = 0; v < N; v++) // (the graph is validated below; the matrix build must not index outside it first)
+			for (int j = 0; j < code->var_deg[v]; j++, e++)
+				if (code->var_deg[v] < 1 || code->var_chk[e] < 0 || code->var_chk[e] >= M || code->var_h[e] <= 0 || code->var_h[e] >= q)
+					return fail_create(nullptr, NBL_ERR_ARG, "variable-side edge out of range");
+		std::vector<std::vector<uint8_t>> rows;
+		const std::string e = osd_matrix(code, p, osd, rows);
+		if (!e.empty()) return fail_create(nullptr, NBL_ERR_ARG, e);
+		osd_R = (int)rows.size();
+		if (osd_R >= n) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "OSD: the matrix has no fewer rows than columns");
+		const int nw = (n + 63) / 64;
+		std::vector<std::vector<uint64_t>> packed(osd_R, std::vector<uint64_t>(nw, 0));
+		for (int r = 0; r < osd_R; r++)
+			for (int c = 0; c < n; c++)
+				if (rows[r][c]) packed[r][c >> 6] |= 1ull << (c & 63);
+		if (gf2_rank(packed, nw) != osd_R)
+			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "OSD: [CRC rows; H_bit] is not of full row rank (the reference's elimination never ends on it)");
+		for (auto &r : packed) osd_words.insert(osd_words.end(), r.begin(), r.end());
 	}
 	if (params->max_iter < 0) return fail_create(nullptr, NBL_ERR_ARG, "max_iter < 0");
 	if (params->method == NBL_METHOD_EMS) {
@@ -349,6 +487,16 @@ extern "C" nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *g
 	    (st = upload(d, c_epos, &d->g.c_epos)) || (st = upload(d, c_var, &d->g.c_var)) || (st = upload(d, c_h, &d->g.c_h)) ||
 	    (st = upload(d, c_hinv, &d->g.c_hinv)) || (st = upload(d, mul8, &d->g.mul)))
 		return fail_create(d, st, "");
+	if (osd_on) {
+		if ((st = upload(d, osd_words, &d->osd.H))) return fail_create(d, st, "");
+		d->osd_on = true;
+		d->osd.R = osd_R;
+		d->osd.n_dist = (int)(N * std::log((double)q) / std::log(2.0)); // compute_min_distance_bit's CodeLen_bit, truncated like it
+		d->osd.order = osd->order < 0 ? 0 : osd->order; // (method 6 runs order 0 when the profile's order is -1)
+		d->osd.flag = params->method == NBL_METHOD_OSD ? 1 : osd->flag;
+		d->osd_factor = osd->factor;
+		d->osd_acc = d->osd.flag == 0;
+	}
 	d->d_e2c_map = (int *)d->g.v_cpos;
 	d->all_dc4 = true;
 	for (int m = 0; m < M; m++) d->all_dc4 = d->all_dc4 && (code->chk_deg[m] == 4);
@@ -532,6 +680,7 @@ struct IterCtx {
 	bool damp, fused;
 	double *bufA, *bufB;
 	const double *zeros = nullptr; // stands in for bufA in iteration 1 (then bufA needs no clearing)
+	int batch = 0;                 // codewords of the call (r.B may shrink to the active list; the OSD sums cover every codeword)
 	// profiling: one event after every launch on the launch stream; phase time = sum of the gaps it closes
 	size_t nev = 0;
 	std::vector<int> tag; // 0 vn, 1 syn, 2 cn, 3 other
@@ -571,6 +720,10 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			else if (d->g.q == 64) HIP_TRY(d, nbl_launch_cn_bp64(d->g, wf, c.r, true, st));
 			else HIP_TRY(d, nbl_launch_cn_bp256(d->g, wf, c.r, true, st));
 			HIP_TRY(d, mark(c, 2, st));
+			if (d->osd_acc) {
+				HIP_TRY(d, nbl_launch_osd_acc(d->w.post, d->osd_S, c.batch, d->g.N, d->g.p, d->g.q, d->osd_factor, it == 1, st));
+				HIP_TRY(d, mark(c, 3, st));
+			}
 			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
 			HIP_TRY(d, mark(c, 1, st));
 			if (count) { d->launches[2]++; d->launches[1]++; }
@@ -578,6 +731,10 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 		}
 		HIP_TRY(d, nbl_launch_vn(d->g, d->w, c.r, c.damp, st));
 		HIP_TRY(d, mark(c, 0, st));
+		if (d->osd_acc) {
+			HIP_TRY(d, nbl_launch_osd_acc(d->w.post, d->osd_S, c.batch, d->g.N, d->g.p, d->g.q, d->osd_factor, it == 1, st));
+			HIP_TRY(d, mark(c, 3, st));
+		}
 		HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
 		HIP_TRY(d, mark(c, 1, st));
 		if (count) { d->launches[0]++; d->launches[1]++; }
@@ -644,7 +801,8 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 	c.bufB = d->c2v_alt;
 	c.zeros = c.fused ? d->c2v_zero : nullptr;
 	// the captured graphs hold buffer addresses and the batch size: any change drops them
-	const nbl_decoder::GraphKey key = {d_Lin, d->w.Lch, d->w.v2c, d->w.c2v, d->c2v_alt, d->w.post, B, d->record_state ? 1 : 0, d->force_generic, c.fused ? 1 : 0};
+	const nbl_decoder::GraphKey key = {d_Lin, d->w.Lch, d->w.v2c, d->w.c2v, d->c2v_alt, d->w.post, d->osd_S, B, d->record_state ? 1 : 0, d->force_generic, c.fused ? 1 : 0};
+	c.batch = B;
 	if (memcmp(&key, &d->gkey, sizeof key) != 0) { drop_graphs(d); d->gkey = key; }
 	HIP_TRY(d, mark(c, 3, st));
 	HIP_TRY(d, nbl_launch_init(d_Lin, d->g, d->w, B, (c.damp ? 1 : 0) | (c.zeros ? 2 : 0), st)); // bit 1: c2v is not cleared
@@ -665,7 +823,8 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 	const bool compact = polling && d->use_compact && !d->use_graph && B >= 1024;
 	d->w.active = nullptr;
 	int pending = -1; // parity of the read-back that has not been looked at yet
-	for (int it_lo = 1, widx = 0; it_lo <= p.max_iter; it_lo += wlen, widx++) {
+	const int max_iter = p.method == NBL_METHOD_OSD ? 0 : p.max_iter; // (method 6: Decoding_OSD_bit alone, no iterations)
+	for (int it_lo = 1, widx = 0; it_lo <= max_iter; it_lo += wlen, widx++) {
 		const int it_hi = (it_lo + wlen - 1 < p.max_iter) ? it_lo + wlen - 1 : p.max_iter;
 		nbl_status s = run_window(c, widx, it_lo, it_hi, st);
 		if (s) { d->w.active = nullptr; return s; }
@@ -687,6 +846,13 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 		}
 	}
 	d->w.active = nullptr;
+	// OSD on every codeword that did not converge (NBLDPC.cpp:769-775: only after at least one iteration), or the whole of method 6
+	if (d->osd_on && (p.method == NBL_METHOD_OSD || p.max_iter > 0)) {
+		NblOsdDev o = d->osd;
+		o.S = d->osd_S;
+		HIP_TRY(d, nbl_launch_osd(d->g, d->w, o, B, st));
+		HIP_TRY(d, mark(c, 3, st));
+	}
 	if (polling) HIP_TRY(d, hipStreamSynchronize(st));
 	if (c.fused && last_it > 0) d->last_c2v = (last_it & 1) ? c.bufB : c.bufA;
 	if (d->profiling && c.nev > 0) {
@@ -1066,4 +1232,17 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 	}
 	(void)hipFree(tmp);
 	return rc;
+}
+
+// Diagnostic only (not part of include/nbldpc.h): the flag-0 OSD posterior sums S of codeword b after the last decode, [N][p]
+extern "C" nbl_status nbl_debug_osd_sums(nbl_decoder *d, int32_t b, double *out)
+{
+	if (!d || !out || b < 0 || b >= d->last_B) return NBL_ERR_ARG;
+	if (!d->osd_S) { d->err = "no OSD sums: OSD post-processing with flag 0 is off"; return NBL_ERR_ARG; }
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	const size_t n = (size_t)d->g.N * d->g.p;
+	HIP_TRY(d, hipMemcpyAsync(out, d->osd_S + (size_t)b * n, n * 8, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	return NBL_OK;
 }

@@ -87,6 +87,24 @@ def gf_tables(q):
     return mul, inv
 
 
+def gf_matrices(q, as_loaded=True):
+    """[q][p][p] uint8: GFElement[e].ValueMatric of every element e, the binary image of "multiply by e" (row i of alpha^k's
+    matrix holds the bits of alpha^(k+i), the Mat.Repr.GF.<q>.txt layout).  as_loaded=True: as CGF::Initial leaves them -- it reads
+    q-2 of the q-1 non-zero elements (GF.cpp:137), so alpha^(q-2)'s matrix stays zero; False: the full set."""
+    import numpy as np
+    mul, _ = gf_tables(q)
+    p = q.bit_length() - 1
+    m = np.zeros((q, p, p), dtype=np.uint8)
+    x = 1
+    for k in range(q - 2 if as_loaded else q - 1):
+        y = x
+        for i in range(p):
+            m[x, i] = [(y >> j) & 1 for j in range(p)]
+            y = mul[y][2]
+        x = mul[x][2]
+    return m
+
+
 def write_gf_tables(q, src_dir):
     """Write Arith.Table.GF.<q>.txt and Mat.Repr.GF.<q>.txt under src_dir (the reference expects ./SRC/)."""
     os.makedirs(src_dir, exist_ok=True)

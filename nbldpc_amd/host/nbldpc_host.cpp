@@ -39,7 +39,6 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	PunctureLen = (int)PuncturePositionV.size();
 	PuncturePosition = PuncturePositionV.data();
 
-	if (sim.OSD_order >= 0) { error = "OSD post-processing is outside this decode path: set OSD_order to -1"; std::cerr << error << std::endl; return false; }
 	if (sim.randomMsg && !InitialEncode()) return false;
 
 	if (device < 0) return true; // host-only use (link-chain front-end, encoder): no decoder handle is created
@@ -64,12 +63,46 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	if (dec) { nbl_destroy(dec); dec = nullptr; }
 	// basic-set T-EMS: its parameters go through the extension struct (NBLDPC.cpp:332-337)
 	nbl_params_ext ext = {sim.bs_tems_nm, sim.bs_tems_nc, sim.bs_tems_factor, sim.bs_tems_offset};
-	nbl_status st = nbl_create_ex(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr, device, &dec);
+	// OSD (method 6, or post-processing when OSD_order >= 0): the element matrices as CGF::Initial leaves them -- it reads q-2 of
+	// the q-1 entries of ./SRC/Mat.Repr.GF.<q>.txt (GF.cpp:115-152), so alpha^(q-2)'s matrix stays zero.  (The reference's order-3
+	// loop also prints "mm" for every frame, OSD.h:166; that debug print is not reproduced.)
+	const bool osd = sim.decodeMethod == OSD_DECODE || sim.OSD_order >= 0;
+	std::vector<uint8_t> gf_mat;
+	if (osd && !LoadMatRepr(gf_mat)) return false;
+	nbl_osd_params op = {sim.OSD_order, sim.OSD_flag, sim.OSD_factor, sim.crcLen, sim.crc_correctLen, gf_mat.data()};
+	nbl_status st = nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
+	                               osd ? &op : nullptr, device, &dec);
 	if (st != NBL_OK) {
 		error = nbl_last_error(nullptr);
 		std::cerr << error << std::endl; // the reference prints and exits for its own configuration errors (NBLDPC.cpp:284-285)
 		return false;
 	}
+	return true;
+}
+
+// [q][p][p] GFElement[e].ValueMatric as CGF::Initial reads them (GF.cpp:115-152): q-2 entries "A^k --> order: k poly: e" each
+// followed by p rows of p bits; element 0 and the element never read keep zero matrices
+bool CNBLDPC::LoadMatRepr(std::vector<uint8_t> &m)
+{
+	int p = 0;
+	while ((1 << p) < GFq) p++;
+	const std::string name = "./SRC/Mat.Repr.GF." + std::to_string(GFq) + ".txt";
+	std::ifstream f(name);
+	if (!f.is_open()) { error = "Cannot open " + name; std::cerr << error << std::endl; return false; }
+	std::string rub;
+	std::getline(f, rub);
+	m.assign((size_t)GFq * p * p, 0);
+	for (int k = 0; k < GFq - 2; k++) {
+		int order = 0, e = 0;
+		f >> rub >> rub >> rub >> order >> rub >> e;
+		if (!f || e <= 0 || e >= GFq) { error = "Malformed " + name; std::cerr << error << std::endl; return false; }
+		for (int i = 0; i < p * p; i++) {
+			int bit = 0;
+			f >> bit;
+			m[(size_t)e * p * p + i] = (uint8_t)bit;
+		}
+	}
+	if (!f) { error = "Malformed " + name; std::cerr << error << std::endl; return false; }
 	return true;
 }
 

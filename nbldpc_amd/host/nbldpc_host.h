@@ -53,6 +53,7 @@ private:
 	std::vector<int> swap_src, swap_dst;
 	std::vector<std::vector<int>> enc_link, enc_coef;
 	bool InitialEncode();
+	bool LoadMatRepr(std::vector<uint8_t> &m);
 	nbl_decoder *dec = nullptr;
 	std::string error;
 };

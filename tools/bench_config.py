@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the other BASELINE.json configurations (parity-test cases, not the headline bench line).
 
-usage: python tools/bench_config.py cfg1|cfg2|cfg3|cfg3nc2|cfg3nm24|cfg3nm48|cfg3nm64|cfg4|cfg5|tems256|ems64|bp64|ems16|tems16|bp16|bstems16|bstems256 [batch] [steps] [ebn0]
+usage: python tools/bench_config.py cfg1|cfg2|cfg3|cfg3osd1|cfg3osd2|cfg4osdf0|cfg3nc2|cfg3nm24|cfg3nm48|cfg3nm64|cfg4|cfg5|tems256|ems64|bp64|ems16|tems16|bp16|bstems16|bstems256 [batch] [steps] [ebn0]
 Prints one JSON line: codewords/s at fixed iterations with HBM-resident inputs, plus the algorithmic-bytes roofline fraction
 (8(q-1)[N + I(N + 4E + D E)] + 4N + 4 bytes per codeword, D = 1 for BP / T-EMS).
 """
@@ -35,6 +35,14 @@ CFG = {
     # basic-set T-EMS (method 7): one check per wave, unfused iteration
     "bstems16": dict(code="divsalar.UNBLDPC.512.256.GF.16", method=nb.METHOD_BS_TEMS, iters=50, batch=8192, kw=dict(bs_nm=4, bs_nc=2), D=1, ebn0=2.0, mod="bpsk"),
     "bstems256": dict(code="divsalar.UNBLDPC.512.256.GF.256", method=nb.METHOD_BS_TEMS, iters=50, batch=2048, kw=dict(bs_nm=8, bs_nc=3), D=1, ebn0=1.5, mod="bpsk"),
+    # OSD post-processing of the frames that do not converge (nbl_osd.hip): cfg3's shape at 0.5 dB, orders 1 and 2, flag 1; cfg4 with
+    # flag 0 (posterior sums accumulated after every variable-node pass)
+    "cfg3osd1": dict(code="divsalar.UNBLDPC.512.256.GF.256", method=nb.METHOD_EMS, iters=50, batch=2048,
+                     kw=dict(ems_nm=32, ems_nc=3, osd_order=1, osd_flag=1), D=0, ebn0=0.5, mod="bpsk"),
+    "cfg3osd2": dict(code="divsalar.UNBLDPC.512.256.GF.256", method=nb.METHOD_EMS, iters=50, batch=2048,
+                     kw=dict(ems_nm=32, ems_nc=3, osd_order=2, osd_flag=1), D=0, ebn0=0.5, mod="bpsk"),
+    "cfg4osdf0": dict(code="BDS.576.288.GF.64", method=nb.METHOD_TEMS, iters=50, batch=2048,
+                      kw=dict(tems_nr=2, tems_nc=3, osd_order=1, osd_flag=0, osd_factor=0.5), D=1, ebn0=3.0, mod="qam"),
     "cfg5": dict(code="divsalar.CNBLDPC.512.256.GF.256", method=nb.METHOD_BP, iters=100, batch=1024, kw=dict(), D=1, ebn0=10.0, mod="qam"),
 }
 
