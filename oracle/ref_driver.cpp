@@ -13,6 +13,7 @@
 // usage (cwd must contain ./SRC/ with the GF tables, see oracle/Makefile):
 //   ref_driver dump <profile> <outdir> <EbN0> <frames> <iters,csv> <state_iters,csv>
 //   ref_driver fer  <profile>
+//   ref_driver decode <profile> <outdir> <llr_file> <frames> <iters,csv> <state_iters,csv> <state frames>
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
@@ -152,6 +153,72 @@ static int run_dump(int argc, char** argv)
 	return 0;
 }
 
+// Decoder alone, on channel LLRs the caller supplies (a raw file of B * N * (q-1) doubles): CSimulation::Initial reads the
+// profile, CNBLDPC::Initial (NBLDPC.cpp:140) the code file, and CNBLDPC::Decoding runs on every frame -- no CComm, so no encoder,
+// channel or code rate is involved.  CNBLDPC::Initial still builds its OSD and CRC matrices (NBLDPC.cpp:380-457): the graph needs
+// (N - M) log2(q) bits above crcLen (8, 16 or 24) and a bit-level H of full row rank, or its eliminations never end.
+// Message state of the first `nstate` frames.
+static int run_decode(int argc, char** argv)
+{
+	if (argc < 9) { fprintf(stderr, "decode: need profile outdir llr_file frames iters state_iters nstate\n"); return 2; }
+	std::string profile = argv[2], outdir = argv[3];
+	const size_t B = (size_t)atoi(argv[5]);
+	std::vector<int> iters = parse_csv(argv[6]);
+	std::vector<int> state_iters = parse_csv(argv[7]);
+	const size_t S = (size_t)atoi(argv[8]);
+
+	CSimulation sim;
+	sim.Initial(profile);
+	CNBLDPC c;
+	c.Initial(sim);
+	const int N = c.CodeLen, q = c.GFq;
+	int E = 0, p = 0;
+	for (int n = 0; n < N; n++) E += c.VarDegree[n];
+	while ((1 << p) < q) p++;
+	std::vector<double> Lch(B * N * (q - 1));
+	FILE* f = fopen(argv[4], "rb");
+	if (!f || fread(Lch.data(), 8, Lch.size(), f) != Lch.size()) { fprintf(stderr, "cannot read %s\n", argv[4]); return 2; }
+	fclose(f);
+	std::vector<double*> rows(N);
+	std::vector<int> dec(N), rely_sym(N), rely_bit((size_t)N * p);
+	std::vector<int32_t> out(iters.size() * B * N), flag(iters.size() * B), synok(iters.size() * B);
+	std::vector<double> st_post(state_iters.size() * S * N * (q - 1));
+	std::vector<double> st_v2c(state_iters.size() * S * E * (q - 1)), st_c2v(state_iters.size() * S * E * (q - 1));
+	for (size_t b = 0; b < B; b++) {
+		for (int n = 0; n < N; n++) rows[n] = &Lch[(b * N + n) * (q - 1)];
+		for (size_t k = 0; k < iters.size(); k++) {
+			c.maxIter = iters[k];
+			int r = c.Decoding(rows.data(), dec.data(), rely_sym.data(), rely_bit.data());
+			for (int n = 0; n < N; n++) out[(k * B + b) * N + n] = dec[n];
+			flag[k * B + b] = r;
+			synok[k * B + b] = syndrome_ok(c, dec.data());
+		}
+		for (size_t k = 0; b < S && k < state_iters.size(); k++) {
+			c.maxIter = state_iters[k];
+			c.Decoding(rows.data(), dec.data(), rely_sym.data(), rely_bit.data());
+			size_t e = 0;
+			for (int n = 0; n < N; n++) {
+				memcpy(&st_post[((k * S + b) * N + n) * (q - 1)], c.L_post[n], sizeof(double) * (q - 1));
+				for (int d = 0; d < c.VarDegree[n]; d++, e++) {
+					int row = c.VarLink[n][d], dc = c.VarLinkDc[n][d];
+					memcpy(&st_v2c[((k * S + b) * E + e) * (q - 1)], c.L_v2c[n][d], sizeof(double) * (q - 1));
+					memcpy(&st_c2v[((k * S + b) * E + e) * (q - 1)], c.L_c2v[row][dc], sizeof(double) * (q - 1));
+				}
+			}
+		}
+	}
+	std::vector<int32_t> it32(iters.begin(), iters.end()), st32(state_iters.begin(), state_iters.end());
+	write_npy(outdir + "/iters.npy", "<i4", {iters.size()}, it32.data(), it32.size() * 4);
+	write_npy(outdir + "/out.npy", "<i4", {iters.size(), B, (size_t)N}, out.data(), out.size() * 4);
+	write_npy(outdir + "/ret.npy", "<i4", {iters.size(), B}, flag.data(), flag.size() * 4);
+	write_npy(outdir + "/syn_ok.npy", "<i4", {iters.size(), B}, synok.data(), synok.size() * 4);
+	write_npy(outdir + "/state_iters.npy", "<i4", {state_iters.size()}, st32.data(), st32.size() * 4);
+	write_npy(outdir + "/st_post.npy", "<f8", {state_iters.size(), S, (size_t)N, (size_t)(q - 1)}, st_post.data(), st_post.size() * 8);
+	write_npy(outdir + "/st_v2c.npy", "<f8", {state_iters.size(), S, (size_t)E, (size_t)(q - 1)}, st_v2c.data(), st_v2c.size() * 8);
+	write_npy(outdir + "/st_c2v.npy", "<f8", {state_iters.size(), S, (size_t)E, (size_t)(q - 1)}, st_c2v.data(), st_c2v.size() * 8);
+	return 0;
+}
+
 // Same control flow as the reference's main() (main.cpp:13-65) with parallel_for replaced by a serial loop
 // (lanes are independent, main.cpp:46).  Prints one machine-readable line per Eb/N0 point.
 static int run_fer(int argc, char** argv)
@@ -180,8 +247,9 @@ static int run_fer(int argc, char** argv)
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { fprintf(stderr, "usage: ref_driver dump|fer ...\n"); return 2; }
+	if (argc < 2) { fprintf(stderr, "usage: ref_driver dump|fer|decode ...\n"); return 2; }
 	if (!strcmp(argv[1], "dump")) return run_dump(argc, argv);
 	if (!strcmp(argv[1], "fer")) return run_fer(argc, argv);
+	if (!strcmp(argv[1], "decode")) return run_decode(argc, argv);
 	return 2;
 }

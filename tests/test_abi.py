@@ -107,3 +107,113 @@ def test_create_refuses_shapes_the_kernels_cannot_run():
     assert e.value.status == -2 and "must not exceed 32" in str(e.value)
     # (EMS at the largest supported shape -- GF(256), check degree 8, nm = q, nc = 6: 71 KB of LDS -- is accepted and run by
     #  tests/test_gpu_parity.py::test_generic_ems_beyond_64k_lds)
+
+
+def _no_device():
+    import torch
+    return not torch.cuda.is_available()
+
+
+def _accepted(code, **kw):
+    """The shape checks of nbl_create precede the device: an accepted shape fails with NBL_ERR_NO_DEVICE on a box without a
+    GPU and makes a decoder on one."""
+    if _no_device():
+        with pytest.raises(nb.NblError) as e:
+            _create(code, **kw)
+        assert e.value.status == -3, str(e.value)
+    else:
+        _create(code, **kw).close()
+
+
+def _with_extra_edges(code, var, checks):
+    """`code` with variable `var` joined to each of `checks` as well (coefficient 1)."""
+    off = np.concatenate([[0], np.cumsum(code.var_deg)])
+    var_rows = [[(int(code.var_chk[e]) + 1, int(code.var_h[e])) for e in range(off[n], off[n + 1])] for n in range(code.N)]
+    var_rows[var] += [(m + 1, 1) for m in checks]
+    chk_rows = [[] for _ in range(code.M)]
+    for n, r in enumerate(var_rows):
+        for m1, h in r:
+            chk_rows[m1 - 1].append((n + 1, h))
+    return nb.Code(spec=dict(N=code.N, M=code.M, q=code.q, var_rows=var_rows, chk_rows=chk_rows))
+
+
+def test_create_enforces_the_degree_envelope():
+    """Checks of degree 2 .. 8 and variables of degree 1 .. 8 (include/nbldpc.h): one more or one less is NBL_ERR_ARG."""
+    ems = dict(method=nb.METHOD_EMS, max_iter=5, ems_nm=4, ems_nc=2)
+    ring = _ring_code(16, 12, 8)                        # checks of degree 8, variables of degree 2
+    assert ring.chk_deg.max() == 8
+    _accepted(ring, **ems)
+    nine = _with_extra_edges(ring, 0, [m for m in range(12) if m not in ring.var_chk[:2]][:1])
+    assert nine.chk_deg.max() == 9 and nine.var_deg.max() == 3
+    with pytest.raises(nb.NblError) as e:
+        _create(nine, **ems)
+    assert e.value.status == -1 and "(8)" in str(e.value)
+    base = _ring_code(16, 12, 4)
+    dv8 = _with_extra_edges(base, 0, [m for m in range(12) if m not in base.var_chk[:2]][:6])
+    assert dv8.var_deg.max() == 8 and dv8.chk_deg.max() == 5
+    _accepted(dv8, **ems)
+    dv9 = _with_extra_edges(base, 0, [m for m in range(12) if m not in base.var_chk[:2]][:7])
+    assert dv9.var_deg.max() == 9 and dv9.chk_deg.max() == 5
+    with pytest.raises(nb.NblError) as e:
+        _create(dv9, **ems)
+    assert e.value.status == -1 and "(8)" in str(e.value)
+    # a check of degree 1: check 0 with one variable of its own and nothing else
+    lone = nb.Code(spec=dict(N=3, M=2, q=16, var_rows=[[(1, 1)], [(2, 2)], [(2, 3)]], chk_rows=[[(1, 1)], [(2, 2), (3, 3)]]))
+    assert lone.chk_deg.min() == 1
+    with pytest.raises(nb.NblError) as e:
+        _create(lone, **ems)
+    assert e.value.status == -1 and "check of degree < 2" in str(e.value)
+    # a variable of degree 0
+    none = nb.Code(spec=dict(N=3, M=1, q=16, var_rows=[[(1, 1)], [(1, 2)], []], chk_rows=[[(1, 1), (2, 2)]]))
+    assert none.var_deg.min() == 0
+    with pytest.raises(nb.NblError) as e:
+        _create(none, **ems)
+    assert e.value.status == -1 and "variable of degree < 1" in str(e.value)
+
+
+def test_create_refuses_tems_path_codes_above_32_bits():
+    """T-EMS: log2(q) * maxdc > 32 is refused -- exactly the cells tests/test_gpu_degrees.py leaves out of its grid, and every
+    (q, maxdc) of the envelope beside them; 32 bits exactly (GF(16) dc 8, GF(256) dc 4) and everything below pass the shape checks."""
+    from degree_util import PROFILES, QS, TEMS_REFUSED, profile_code
+    tems = dict(method=nb.METHOD_TEMS, max_iter=5, tems_nr=2, tems_nc=2)
+    for profile in PROFILES:
+        for q in QS:
+            code, _, _ = profile_code(profile, q, "tems")
+            p = q.bit_length() - 1
+            assert ((profile, q) in TEMS_REFUSED) == (p * int(code.chk_deg.max()) > 32), (profile, q)
+            if (profile, q) in TEMS_REFUSED:
+                with pytest.raises(nb.NblError) as e:
+                    _create(code, **tems)
+                assert e.value.status == -2 and "must not exceed 32" in str(e.value), (profile, q)
+            else:
+                _accepted(code, **tems)
+    for q in QS:
+        p = q.bit_length() - 1
+        for dc in (2, 4, 6, 8):
+            code = _ring_code(q, 12, dc)
+            if p * dc > 32:
+                with pytest.raises(nb.NblError) as e:
+                    _create(code, **tems)
+                assert e.value.status == -2 and "must not exceed 32" in str(e.value), (q, dc)
+            else:
+                _accepted(code, **tems)
+    assert _ring_code(16, 12, 8).chk_deg.max() * 4 == 32 and _ring_code(256, 12, 4).chk_deg.max() * 8 == 32
+
+
+def test_create_refuses_ems_shapes_above_160_kb_of_lds():
+    """General EMS kernel, bytes of LDS for one check (nbl_api.cpp): (maxdc q + (2 layers + 1) q + maxdc nm) 8 + maxdc nm 4 + 16
+    with layers = nc + 1 below nc = maxdc - 1, else 1.  Inside the envelope the other checks of nbl_create leave (q <= 256,
+    degrees <= 8, nm <= q) the largest value is 71,696 B (GF(256), check degree 8, nm = 256, nc = 6), so NO accepted shape
+    reaches the 160 KB refusal: there is no 'just above' shape to create, and the one nearest to the bound must be accepted.
+    The shapes one step outside the envelope are refused by the earlier checks, each with its own status."""
+    def lds(q, maxdc, nm, nc):
+        layers = 1 if nc >= maxdc - 1 else nc + 1
+        return (maxdc * q + (2 * layers + 1) * q + maxdc * nm) * 8 + maxdc * nm * 4 + 16
+    worst = max((lds(q, dc, nm, nc), q, dc, nm, nc) for q in (4, 8, 16, 32, 64, 128, 256) for dc in range(2, 9)
+                for nm in (1, q // 2, q) for nc in range(0, 9))
+    assert worst == (71696, 256, 8, 256, 6) and worst[0] < 160 * 1024
+    _accepted(_ring_code(256, 12, 8), method=nb.METHOD_EMS, max_iter=5, ems_nm=256, ems_nc=6)
+    assert lds(512, 8, 512, 6) < 160 * 1024 < lds(1024, 8, 1024, 6)   # (where the bound would bite: fields the library refuses)
+    with pytest.raises(nb.NblError) as e:                             # nm above q
+        _create(_ring_code(256, 12, 8), method=nb.METHOD_EMS, max_iter=5, ems_nm=257, ems_nc=6)
+    assert e.value.status == -1 and "EMS_Nm is too large" in str(e.value)

@@ -128,3 +128,91 @@ def test_fixed_iterations_freeze_output(oracle):
     for b in range(4):
         r, out, it = dec.decode(L[b])
         assert np.array_equal(out, g["out"][k, b]) and r == g["syn_ok"][k, b]
+
+
+# ---- degrees outside the shipped codes (checks 2 .. 8, variables 1 .. 8): fixtures of tests/golden/make_golden_degrees.py -------------
+DEG_SETS = ["deg_all_gf16_ems", "deg_all_gf16_tems", "deg_all_gf16_bp", "deg_dc78_gf64_ems", "deg_dv48_gf4_tems", "deg_dc2_gf256_bp"]
+DEG_BS_SETS = ["deg_all_gf16_bstems"]
+
+
+def _mk_deg(oracle, meta, max_iter, mode):
+    from degree_util import spec_edges
+    _, edges = spec_edges(meta["spec"])
+    return oracle.Decoder(oracle.Code(edges=edges), oracle.GF(edges[2]), meta["profile"]["method"], int(max_iter), mode,
+                          **decoder_kwargs(meta["profile"]))
+
+
+def _check_deg(oracle, name, mode, exact):
+    g, meta = load_golden(name)
+    assert min(meta["chk_degs"]) < 4 or max(meta["chk_degs"]) > 5 or max(meta["var_degs"]) > 2  # outside the shipped codes' box
+    L = g["L_ch"]
+    bp = meta["profile"]["method"] == 1
+    frames = range(L.shape[0])
+    for k, it in enumerate(g["iters"]):
+        dec = _mk_deg(oracle, meta, it, mode)
+        for b in frames:
+            r, out, _ = dec.decode(L[b])
+            assert np.array_equal(out, g["out"][k, b]) and r == g["syn_ok"][k, b], (name, int(it), b)
+            assert bp or r == g["ret"][k, b]
+    for k, it in enumerate(g["state_iters"]):
+        dec = _mk_deg(oracle, meta, it, mode)
+        for li, lane in enumerate(g["state_lanes"]):
+            dec.decode(L[lane])
+            for nm, a, ref in zip(("post", "v2c", "c2v"), dec.state(), (g["st_post"][k, li], g["st_v2c"][k, li], g["st_c2v"][k, li])):
+                if exact:
+                    assert np.array_equal(a, ref), (name, nm, int(it), int(lane))
+                else:
+                    assert np.max(np.abs(a - ref)) <= LLR_TOL * max(1.0, np.max(np.abs(ref))), (name, nm, int(it), int(lane))
+
+
+@pytest.mark.parametrize("name", DEG_SETS)
+def test_degree_fixtures_literal_bit_exact(oracle, name):
+    """The literal oracle equals the compiled reference bit for bit on graphs with checks of degree 2 .. 8 and variables of degree
+    1 .. 8: decisions and flags of all 8 frames at every recorded iteration count, message state of two frames."""
+    _check_deg(oracle, name, oracle.LITERAL, exact=True)
+
+
+@pytest.mark.parametrize("name", DEG_SETS)
+def test_degree_fixtures_canonical_matches_reference_decisions(oracle, name):
+    _check_deg(oracle, name, oracle.CANONICAL, exact=False)
+
+
+@pytest.mark.parametrize("name", ["deg_all_gf16_ems", "deg_dc78_gf64_ems"])
+def test_degree_fixtures_ems_dynamic_program_equals_enumeration(oracle, name):
+    """test_ems_dynamic_program_equals_enumeration on checks of degree 2 .. 8 in one graph, and of degree 7 / 8 over GF(64)."""
+    g, meta = load_golden(name)
+    L = g["L_ch"]
+    it = int(g["iters"][-1])
+    a, b = _mk_deg(oracle, meta, it, oracle.CANONICAL), _mk_deg(oracle, meta, it, oracle.CANONICAL_DFS)
+    for f in range(min(4, L.shape[0])):
+        ra, oa, ia = a.decode(L[f])
+        rb, ob, ib = b.decode(L[f])
+        assert (ra, ia) == (rb, ib) and np.array_equal(oa, ob)
+        for x, y in zip(a.state(), b.state()):
+            assert np.array_equal(x, y)
+
+
+@pytest.mark.parametrize("name", DEG_BS_SETS)
+def test_degree_fixtures_bstems_checker(tmp_path, name):
+    """BS-TEMS has its own restatement (tests/bstems_check.cpp): literal mode bit for bit, canonical mode decisions / flags equal and
+    state within 1e-9, on the graph with every degree."""
+    from bstems_util import CANONICAL, LITERAL, bs_kwargs, build_checker, run_checker
+    from degree_util import spec_edges
+    exe = build_checker(tmp_path)
+    g, meta = load_golden(name)
+    code, _ = spec_edges(meta["spec"])
+    kw = bs_kwargs(meta["profile"])
+    L = g["L_ch"]
+    lanes = [int(b) for b in g["state_lanes"]]
+    for mode in (LITERAL, CANONICAL):
+        for k, it in enumerate(g["iters"]):
+            out, ret, _, _ = run_checker(exe, code, L, int(it), mode, **kw)
+            assert np.array_equal(out, g["out"][k]) and np.array_equal(ret, g["ret"][k]) and np.array_equal(ret, g["syn_ok"][k]), (name, mode, int(it))
+        for k, it in enumerate(g["state_iters"]):
+            _, _, _, st = run_checker(exe, code, L, int(it), mode, **kw, state=lanes)
+            for li, b in enumerate(lanes):
+                for a, ref in zip(st[b], (g["st_post"][k, li], g["st_v2c"][k, li], g["st_c2v"][k, li])):
+                    if mode == LITERAL:
+                        assert np.array_equal(a, ref), (name, int(it), b)
+                    else:
+                        assert np.max(np.abs(a - ref)) <= LLR_TOL * max(1.0, np.max(np.abs(ref))), (name, int(it), b)
