@@ -9,7 +9,16 @@ Build-container only, like make_golden.py, whose driver calls and packing it reu
                 that most frames go through OSD.  osd_flag0_gf16 keeps the posteriors of frame 0 after every iteration 1..5, from
                 which the flag-0 reliabilities are rebuilt.
 
-usage: python tests/golden/make_golden_osd.py [set ... | fer:<set> ...]      (no argument: everything)
+  osd_shape_*.npz  the synthetic shapes of tests/osd_shapes.py (bit lengths that are no multiple of 64, GF(4) .. GF(128), k = 1 and 2,
+                high and low rate, n up to 1024), decoded by `ref_driver decode` on a graph file written by
+                degree_util.write_spec_code_file.  One file per shape: for every order of `orders`, method 6 on every frame (out_m6)
+                and EMS post-processing after 1 and 2 iterations (out, ret, syn_ok [order][k][B]).  Frames: tests/osd_shapes.py
+                ::fixture_frames, real-valued and free of ties.  The rank of [CRC rows; H_bit] is checked in Python first
+                (osd_shapes.shape), because the reference never ends on a deficient one; the 20 s limit per run stays, except where
+                SHAPE_SETS names another (the reference re-encodes every candidate from scratch: about 25 s per frame at order 2
+                and n = 1023 / 1024).
+
+usage: python tests/golden/make_golden_osd.py [set ... | fer:<set> ... | shape:<set> ...]      (no argument: everything)
 """
 import json
 import os
@@ -93,15 +102,87 @@ def run_fer(names):
     json.dump(anchors, open(path, "w"), indent=1)
 
 
+# name -> (shape, orders, frames per order (None: all eight), flag, time limit per run in seconds).  Orders 3 and 5 where k <= 64.
+# At n >= 897 order 2 runs on the first two frames only (the reference's time, above); orders 0 and 1 on all eight.
+SHAPE_SETS = {
+    "osd_shape_one_word": ("one_word", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_just_over_64": ("just_over_64", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_gf8_odd": ("gf8_odd", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_gf8_odd_flag0": ("gf8_odd", [1], {}, 0, 20),
+    "osd_shape_gf8_trunc": ("gf8_trunc", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_gf128": ("gf128", [0, 1, 2], {}, 1, 20),
+    "osd_shape_trunc_on_boundary": ("trunc_on_boundary", [0, 1, 2], {2: 2}, 1, 600),
+    "osd_shape_just_over_512": ("just_over_512", [0, 1, 2], {}, 1, 120),
+    "osd_shape_below_cap": ("below_cap", [0, 1, 2], {2: 2}, 1, 600),
+    "osd_shape_cap": ("cap", [0, 1, 2], {2: 2}, 1, 600),
+    "osd_shape_high_rate": ("high_rate", [0, 1, 2], {}, 1, 60),
+    "osd_shape_low_rate": ("low_rate", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_k1": ("k1", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_k2": ("k2", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_crc16_rows5": ("crc16_rows5", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_crc24_rows1": ("crc24_rows1", [0, 1, 2, 3, 5], {}, 1, 20),
+    "osd_shape_irregular": ("irregular", [0, 1, 2, 3, 5], {}, 1, 20),
+}
+FLAG0_FACTOR = 0.75
+
+
+def run_shape_set(name):
+    import numpy as np
+    sys.path[:0] = [mg.ROOT, os.path.join(mg.ROOT, "tests")]
+    import degree_util as du
+    import osd_shapes as sh
+    shape, orders, cut, flag, limit = SHAPE_SETS[name]
+    code, _, spec, info = sh.shape(shape)   # (asserts the full rank: the reference would never end otherwise)
+    q = code.q
+    L = sh.fixture_frames(shape)
+    iters = [1, 2, 3] if not flag else [1, 2]
+    st_iters = [1, 2, 3] if not flag else []
+    kw = dict(method=2, ems_nm=min(q, 6), ems_nc=2, osd_flag=flag, osd_factor=FLAG0_FACTOR if not flag else 0.0,
+              crc_len=info["crc_len"], crc_correct=info["crc_rows"])
+    arrs = dict(L_ch=L, orders=np.array(orders, np.int32), iters=np.array(iters, np.int32), state_iters=np.array(st_iters, np.int32))
+    tmp = tempfile.mkdtemp(prefix="golden_")
+    du.write_spec_code_file(spec, os.path.join(tmp, "code.txt"))
+    t0 = time.time()
+    for o in orders:
+        B = cut.get(o, L.shape[0])
+        L[:B].tofile(os.path.join(tmp, "L_ch.bin"))
+        for method in ((2, 6) if flag else (2,)):
+            pk = dict(kw, method=method, osd_order=o, gfq=q, code=os.path.join(tmp, "code.txt"), max_iter=max(iters), parallel=1, random_msg=0,
+                      constellation="/root/reference/BPSK.txt")
+            prof = os.path.join(tmp, "profile.txt")
+            open(prof, "w").write(profile_text(**pk))
+            its = iters if method == 2 else [1]
+            subprocess.check_call([os.path.join(mg.ROOT, "oracle", "_ref", "ref_driver_O2"), "decode", prof, tmp, os.path.join(tmp, "L_ch.bin"),
+                                   str(B), ",".join(map(str, its)), ",".join(map(str, st_iters if method == 2 else [])), str(B)],
+                                  cwd=mg.RUN, stderr=subprocess.DEVNULL, stdout=subprocess.DEVNULL, timeout=limit)
+            got = {k: np.load(os.path.join(tmp, k + ".npy")) for k in ("out", "ret", "syn_ok", "st_post")}
+            if method == 6:
+                arrs[f"out_m6_o{o}"] = got["out"][0]
+            else:
+                arrs[f"out_o{o}"], arrs[f"ret_o{o}"], arrs[f"syn_ok_o{o}"] = got["out"], got["ret"], got["syn_ok"]
+                if st_iters:
+                    arrs["st_post"] = got["st_post"]
+                assert (got["ret"][0] == 0).sum() * 2 >= B, (name, o, got["ret"].tolist())   # at least half go through OSD
+    meta = dict(profile=dict(kw, gfq=q, max_iter=max(iters)), shape=shape, spec=spec, seed=sh.SHAPES[shape]["seed"], build="O2",
+                reference_flags="-std=c++14 -O2 -ffp-contract=off, g++ 11.4, x86-64")
+    path = os.path.join(mg.GOLD, name + ".npz")
+    np.savez_compressed(path, meta=json.dumps(meta), **arrs)
+    shutil.rmtree(tmp)
+    print(f"{name}: N={code.N} n={info['n']} ret={[arrs[f'ret_o{o}'].tolist() for o in orders[:1]]} "
+          f"(reference {time.time() - t0:.1f}s, {os.path.getsize(path) / 1e3:.0f} kB)", flush=True)
+
+
 def run_set(name):
     mg.SETS[name] = SETS[name]
     mg.run_set(name)
 
 
 if __name__ == "__main__":
-    args = sys.argv[1:] or list(SETS) + ["fer:" + k for k in FER_SETS]
+    args = sys.argv[1:] or list(SETS) + ["fer:" + k for k in FER_SETS] + ["shape:" + k for k in SHAPE_SETS]
     for a in args:
-        if not a.startswith("fer:"):
+        if a.startswith("shape:"):
+            run_shape_set(a[6:])
+        elif not a.startswith("fer:"):
             run_set(a)
     fer = [a[4:] for a in args if a.startswith("fer:")]
     if fer:

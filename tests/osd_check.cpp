@@ -10,10 +10,15 @@
 // double: 575 of the 576 bits of the BDS code, whose last bit therefore always keeps the base word's value.
 // Equal reliabilities are ordered by index (a stable sort); the reference's std::sort is not stable.
 //
-// usage: osd_check in.bin out.bin
+// usage: osd_check in.bin out.bin [counters.bin]
 //   in:  int32 header [N, M, q, E, order, flag, B, crc_len, crc_rows], int32 var_deg[N], var_chk[E], var_h[E] (variable-major,
 //        0-based), uint8 gf_mat[q][p][p], float64 L_ch[B][N][q-1], and for flag 0: float64 S[B][N p], int32 base[B][N]
 //   out: int32 out[B][N]
+//   counters (optional; what the GPU tests assert their coverage on -- the decoding output does not depend on it): float64 [B][7] per
+//        frame: order rotations of the elimination, pivot repairs, the largest num_temp at which a rotation happened (-1: none), the
+//        flip count of the winner (0 - 3; -1: no candidate below 1,000,000, the base word stays), whether the output differs from the
+//        base word, whether the winner's bit at position nd (the first one the distance leaves out) differs from the base word's
+//        (0 when nd == N p or nobody won), and the smallest distance of any candidate
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -52,7 +57,9 @@ static void g_gauss(Mat &M, int col_length, int row_length, std::vector<int> &or
 				for (int i = 0; i < col_length; i++) M[up][i] ^= M[row][i];
 }
 
-static void h_gauss(Mat &M, int col_length, int row_length, std::vector<int> &order)
+struct Counters { int rotations = 0, repairs = 0, max_rot = -1; };
+
+static void h_gauss(Mat &M, int col_length, int row_length, std::vector<int> &order, Counters &cnt)
 {
 	for (int row = row_length - 1; row >= 0; row--) {
 		int num_temp = row + col_length - row_length;
@@ -63,9 +70,12 @@ static void h_gauss(Mat &M, int col_length, int row_length, std::vector<int> &or
 				if (M[up][col] != 0) {
 					for (int i = 0; i < col_length; i++) M[row][i] ^= M[up][i];
 					ex = true;
+					cnt.repairs++;
 					break;
 				}
 			if (!ex) {
+				cnt.rotations++;
+				cnt.max_rot = std::max(cnt.max_rot, num_temp);
 				row++;
 				for (int i = num_temp - 1; i >= 0; i--) std::swap(order[i], order[i + 1]);
 			}
@@ -133,6 +143,7 @@ int main(int argc, char **argv)
 	}
 	const int ord = order_ > 3 ? 3 : order_;
 	std::vector<int> out((size_t)B * N);
+	std::vector<double> counters((size_t)B * 7);
 	for (int b = 0; b < B; b++) {
 		const double *Lb = &L[(size_t)b * N * (q - 1)];
 		std::vector<double> Lbit(n), rel(n);
@@ -159,7 +170,8 @@ int main(int argc, char **argv)
 		for (int i = 0; i < crcRate; i++)
 			for (int j = 0; j < msg; j++) A[i][j] = partH[i][j];
 		for (int i = 0; i < Mb; i++) A[crcRate + i] = H[i];
-		h_gauss(A, n, R, order);
+		Counters cnt;
+		h_gauss(A, n, R, order, cnt);
 		const int k = n - R;
 		auto encode = [&](const std::vector<int> &in, std::vector<int> &o) { // OSD_Encode_bit
 			o = in;
@@ -184,12 +196,17 @@ int main(int argc, char **argv)
 		int min_distance = 1000000;
 		const int nd = N * std::log(q) / std::log(2);
 		std::vector<int> near = base_bit, cand(n);
+		int win_flips = -1, win_nd_bit = 0;
+		double best = HUGE_VAL;
 		auto consider = [&](int i, int j, int l) {
 			for (int x = 0; x < n; x++) cand[x] = c0[x] ^ (i >= 0 ? g[i][x] : 0) ^ (j >= 0 ? g[j][x] : 0) ^ (l >= 0 ? g[l][x] : 0);
 			double t = 0;
 			for (int x = 0; x < nd; x++)
 				if ((Lbit[x] < 0 && cand[x] == 1) || (Lbit[x] > 0 && cand[x] == 0)) t = t + std::fabs(Lbit[x]);
+			best = std::min(best, t);
 			if (t < min_distance) { // (the copy covers the same nd positions: the rest keep the base word's bits, OSD.h:432-436)
+				win_flips = (i >= 0) + (j >= 0) + (l >= 0);
+				win_nd_bit = nd < n && cand[nd] != base_bit[nd];
 				min_distance = (int)t;
 				std::copy(cand.begin(), cand.begin() + nd, near.begin());
 			}
@@ -209,9 +226,16 @@ int main(int argc, char **argv)
 			for (int j = 0; j < p; j++) a = 2 * a + near[i * p + p - 1 - j];
 			out[(size_t)b * N + i] = a;
 		}
+		double *c = &counters[(size_t)b * 7];
+		c[0] = cnt.rotations; c[1] = cnt.repairs; c[2] = cnt.max_rot; c[3] = win_flips; c[4] = near != base_bit; c[5] = win_nd_bit; c[6] = best;
 	}
 	FILE *fo = fopen(argv[2], "wb");
 	if (!fo || fwrite(out.data(), 4, out.size(), fo) != out.size()) return 2;
 	fclose(fo);
+	if (argc > 3) {
+		FILE *fc = fopen(argv[3], "wb");
+		if (!fc || fwrite(counters.data(), 8, counters.size(), fc) != counters.size()) return 2;
+		fclose(fc);
+	}
 	return 0;
 }

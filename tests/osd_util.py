@@ -34,8 +34,12 @@ def decide(post):
     return np.where(mx > 0, post.argmax(axis=-1) + 1, 0).astype(np.int32)
 
 
-def run_checker(exe, code, L_ch, order, flag=1, crc_len=8, crc_rows=0, gf_mat=None, S=None, base=None):
-    """OSD of every codeword of L_ch [B][N][q-1]; flag 0 takes S [B][N p] and base [B][N].  Returns out [B][N]."""
+COUNTERS = ("rotations", "repairs", "max_rot", "flips", "differs", "nd_bit", "best")
+
+
+def run_checker(exe, code, L_ch, order, flag=1, crc_len=8, crc_rows=0, gf_mat=None, S=None, base=None, counters=False):
+    """OSD of every codeword of L_ch [B][N][q-1]; flag 0 takes S [B][N p] and base [B][N].  Returns out [B][N]; with counters=True
+    also the checker's per-frame counters as a dict of [B] arrays (COUNTERS, described at the head of tests/osd_check.cpp)."""
     import nbldpc_amd as nb
     L_ch = np.ascontiguousarray(L_ch, dtype=np.float64)
     B, N, w = L_ch.shape
@@ -54,8 +58,13 @@ def run_checker(exe, code, L_ch, order, flag=1, crc_len=8, crc_rows=0, gf_mat=No
             if not flag:
                 f.write(np.ascontiguousarray(S, dtype=np.float64).tobytes())
                 f.write(np.ascontiguousarray(base, dtype=np.int32).tobytes())
-        subprocess.check_call([exe, fin, fout])
-        return np.fromfile(fout, dtype=np.int32).reshape(B, N)
+        if not counters:
+            subprocess.check_call([exe, fin, fout])
+            return np.fromfile(fout, dtype=np.int32).reshape(B, N)
+        fcnt = os.path.join(tmp, "cnt.bin")
+        subprocess.check_call([exe, fin, fout, fcnt])
+        c = np.fromfile(fcnt, dtype=np.float64).reshape(B, len(COUNTERS))
+        return np.fromfile(fout, dtype=np.int32).reshape(B, N), {k: c[:, i] for i, k in enumerate(COUNTERS)}
 
 
 def flag0_sums(posts, factor):

@@ -14,7 +14,8 @@ from osd_util import build_checker, decide, flag0_sums, osd_kwargs, profile, run
 
 pytestmark = pytest.mark.gpu
 
-SETS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "osd_*.npz")))
+# (the osd_shape_* fixtures of the synthetic shapes hold several orders per file: tests/test_gpu_osd_shapes.py runs them)
+SETS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "osd_*.npz")) if not os.path.basename(p).startswith("osd_shape_"))
 U512_256 = "divsalar.UNBLDPC.512.256.GF.256"
 BDS = "BDS.576.288.GF.64"
 U512_16 = "divsalar.UNBLDPC.512.256.GF.16"

@@ -8,6 +8,7 @@ import pytest
 
 import nbldpc_amd as nb
 from conftest import GOLD, load_golden
+from degree_util import spec_edges
 from osd_util import build_checker, decide, flag0_sums, osd_kwargs, profile, run_checker
 
 SETS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "osd_*.npz")))
@@ -45,14 +46,54 @@ def test_fixtures_cover_the_issue_grid():
     assert seen == {1, 2, 4, 6, 7}
 
 
+def test_shape_fixtures_cover_the_issue_grid():
+    """osd_shape_*: the shapes, orders and the flag-0 set the fixtures must hold."""
+    import osd_shapes as sh
+    metas = {s: load_golden(s) for s in SETS if s.startswith("osd_shape_")}
+    shapes = {m["shape"] for _, m in metas.values()}
+    assert shapes >= {"gf8_odd", "gf8_trunc", "trunc_on_boundary", "gf128", "just_over_64", "just_over_512", "below_cap", "cap", "k1", "k2",
+                      "high_rate", "low_rate", "one_word", "irregular"} | set(sh.CRC_PARTIAL)
+    flag0 = [m["shape"] for _, m in metas.values() if m["profile"]["osd_flag"] == 0]
+    assert any(sh.SHAPES[x]["q"] == 8 for x in flag0)
+    for name, (g, m) in metas.items():
+        if m["profile"]["osd_flag"] == 1:
+            want = {0, 1, 2} | ({3, 5} if sh.shape(m["shape"])[3]["k"] <= 64 else set())
+            assert set(g["orders"].tolist()) == want, name
+        assert np.array_equal(g["L_ch"], sh.fixture_frames(m["shape"])), name   # (the frames the GPU tests' coverage was chosen on)
+
+
 @pytest.mark.parametrize("name", SETS)
 def test_checker_equals_reference_on_every_osd_frame(checker, name):
     g, meta = load_golden(name)
     p = profile(meta)
-    code = nb.Code(meta["code"])
     kw = osd_kwargs(p)
     L = g["L_ch"]
     checked = 0
+    if "spec" in meta:
+        # a synthetic shape (tests/osd_shapes.py): several orders in one file, method 6 on every frame and EMS post-processing
+        code, _ = spec_edges(meta["spec"])
+        for o in g["orders"]:
+            o = int(o)
+            B = g[f"out_o{o}"].shape[1]   # (order 2 at n >= 897: the first frames only, the reference's time)
+            if p["osd_flag"] == 1:
+                c_out = run_checker(checker, code, L[:B], o, 1, kw["crc_len"], kw["crc_rows"])
+                assert np.array_equal(c_out, g[f"out_m6_o{o}"]), (name, o, "method 6")
+                checked += B
+            for k, T in enumerate(g["iters"]):
+                lanes = np.flatnonzero(g[f"ret_o{o}"][k] == 0)
+                if p["osd_flag"] == 1:
+                    assert np.array_equal(c_out[lanes], g[f"out_o{o}"][k][lanes]), (name, o, int(T))
+                else:
+                    st = list(g["state_iters"])
+                    posts = [[g["st_post"][st.index(t), b] for t in range(1, int(T) + 1)] for b in lanes]
+                    S = np.array([flag0_sums(ps, p["osd_factor"]) for ps in posts])
+                    base = np.array([decide(ps[-1]) for ps in posts])
+                    f_out = run_checker(checker, code, L[lanes], o, 0, kw["crc_len"], kw["crc_rows"], S=S, base=base)
+                    assert np.array_equal(f_out, g[f"out_o{o}"][k][lanes]), (name, o, int(T))
+                checked += len(lanes)
+        assert checked > 0, name
+        return
+    code = nb.Code(meta["code"])
     if p["osd_flag"] == 1 or p["method"] == 6:
         c_out = run_checker(checker, code, L, kw["osd_order"], 1, kw["crc_len"], kw["crc_rows"])
         for k in range(len(g["iters"])):
