@@ -190,6 +190,47 @@ nbl_status nbl_decode_batch_resident(nbl_decoder *dec, int32_t slot, double sigm
 /* state <- state after `draws` calls of CRand::Rand_Uniform (Rand.cpp:17-28); pure host arithmetic */
 void nbl_rand_advance(uint32_t state[3], uint64_t draws);
 
+/* ---- transmit side and error count on the device --------------------------------------------------------------------------
+ * Replaces, for a batch of lanes, CComm::GenerateMessage (PN register, Comm.cpp:181-252), CRCEncode (:506-561), CNBLDPC::Encode
+ * (NBLDPC.cpp:562-604), the symbol -> bit unpacking, Puncture and Modulate (Comm.cpp:255-325) and, after the decode, TakeDecoded +
+ * Err (Comm.cpp:421-493).  Legal after nbl_set_demodulator WITH the constellation points.
+ *   gen        [N][K] uint16, K = N - M: the encoder as a dense linear map, code[n] = sum_k gen[n][k] * msg[k] over GF(q), the final
+ *              column exchanges of CNBLDPC::Encode (NBLDPC.cpp:588-597) included.  H * gen = 0 is checked on the host with the
+ *              decoder's own graph and tables (NBL_ERR_ARG otherwise).  May be NULL when random_msg == 0.
+ *   crc_len    sim.crcLen: 0, 8, 16 or 24 (NBL_ERR_ARG otherwise); above K p: NBL_ERR_UNSUPPORTED
+ *   random_msg sim.randomMsg: 0 = all-zero message AND all-zero codeword, encoder skipped (Comm.cpp:258-268)
+ *   parallel   sim.parallel, the PN stride: every message bit costs `parallel` clocks of the register (Comm.cpp:201-202)
+ *   punct      [n_punct] punctured symbol positions, ascending (Comm.cpp:290-308)
+ *   mod_order, n_mod_sym   must repeat the demodulator's (NBL_ERR_ARG otherwise); mod_order above 256 is NBL_ERR_UNSUPPORTED
+ * Shapes the kernels do not serve (N p above 65536 bits, a matrix above 64 MiB) are NBL_ERR_UNSUPPORTED at this call. */
+typedef struct nbl_tx_desc {
+	const uint16_t *gen;
+	int32_t crc_len, random_msg, parallel;
+	const int32_t *punct;
+	int32_t n_punct;
+	int32_t mod_order, n_mod_sym;
+} nbl_tx_desc;
+nbl_status nbl_set_transmitter(nbl_decoder *dec, const nbl_tx_desc *tx);
+/* nbl_channel_batch with tx_index produced on the device (same slots, same second stream, same threading contract).
+ *   pn_state   HOST [B] uint16: each lane's 11-bit PN register in front of the frame, bit i = regPN[i].  The frame consumes
+ *              (K p - crc_len) * parallel clocks when random_msg != 0 (none otherwise); the caller moves its copy on with nbl_pn_advance.
+ *   lane_state as nbl_channel_batch
+ * The slot keeps, on the device, the code word and with it the transmitted message AS Encode LEAVES IT: the first K code symbols
+ * after the exchanges (NBLDPC.cpp:598-601, Comm.cpp:281-285) -- what Err compares against, not the PN draw. */
+nbl_status nbl_transmit_batch(nbl_decoder *dec, int32_t slot, const uint16_t *pn_state, const uint32_t *lane_state, double sigma, int32_t B);
+/* state <- the register after `clocks` calls of GenPN (Comm.cpp:241-252); pure host arithmetic */
+void nbl_pn_advance(uint16_t *state, uint64_t clocks);
+/* Comm.cpp:421-493 per lane, between the outputs of the last nbl_decode_batch_resident on `slot` (kept on the device once a
+ * transmitter is set) and the slot's transmitted message.  HOST arrays [B]: err_sym, err_bit (message part only), crc_ok =
+ * CrcCheck(RX_MSG_BIT, K p, crc_len, 1) literally: polynomial type 1 for CRC-24 (the encoder used type 0), 1 when crc_len == 0, 0 for
+ * an all-zero word.  With a transmitter set, nbl_decode_batch_resident accepts out_sym == NULL. */
+nbl_status nbl_count_errors(nbl_decoder *dec, int32_t slot, int32_t B, int32_t *err_sym, int32_t *err_bit, uint8_t *crc_ok);
+/* The plain encoder (host buffers): code [B][N] = gen * msg [B][K]; msg_out (may be NULL) = the first K code symbols. */
+nbl_status nbl_encode_batch(nbl_decoder *dec, const int32_t *msg, int32_t B, int32_t *code, int32_t *msg_out);
+/* What a slot holds for lanes b0 .. b0 + n - 1 (any pointer may be NULL): tx_msg [n][K], tx_code [n][N] int32, tx_index [n][L]
+ * uint8.  For parity tests. */
+nbl_status nbl_read_transmitted(nbl_decoder *dec, int32_t slot, int32_t b0, int32_t n, int32_t *tx_msg, int32_t *tx_code, uint8_t *tx_index);
+
 /* Message state of codeword b after the last decode call (host buffers, any may be NULL):
  * post [N][q-1], v2c [E][q-1], c2v [E][q-1], edges in variable-major order.  For parity tests.
  * post and c2v are the reference's members at return.  v2c differs for a codeword that CONVERGED at iteration k >= 2: the

@@ -18,6 +18,7 @@ METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 # every symbol include/nbldpc.h declares
 EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
+           "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
            "nbl_workspace_bytes")
 
@@ -218,13 +219,74 @@ class Decoder:
         self.lib.nbl_channel_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32]
         self._chk(self.lib.nbl_channel_batch(self.h, slot, tx_index.ctypes.data, lane_state.ctypes.data, sigma, tx_index.shape[0]))
 
-    def decode_resident(self, slot, sigma, B):
-        out = np.zeros((B, self.code.N), dtype=np.int32)
+    def decode_resident(self, slot, sigma, B, want_out=True):
+        """want_out=False: out_sym = NULL (legal once a transmitter is set), the first element returned is None"""
+        out = np.zeros((B, self.code.N), dtype=np.int32) if want_out else None
         conv = np.zeros(B, dtype=np.uint8)
         iters = np.zeros(B, dtype=np.int32)
         self.lib.nbl_decode_batch_resident.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._chk(self.lib.nbl_decode_batch_resident(self.h, slot, sigma, B, out.ctypes.data, conv.ctypes.data, iters.ctypes.data))
+        self._chk(self.lib.nbl_decode_batch_resident(self.h, slot, sigma, B, out.ctypes.data if want_out else None, conv.ctypes.data, iters.ctypes.data))
         return out, conv, iters
+
+    def set_transmitter(self, gen, crc_len, random_msg, parallel, punct, mod_order, n_mod_sym):
+        """gen [N][K] uint16 (None with random_msg = 0); punct: punctured symbol positions, ascending"""
+        class TxDesc(C.Structure):
+            _fields_ = [("gen", C.c_void_p), ("crc_len", C.c_int32), ("random_msg", C.c_int32), ("parallel", C.c_int32), ("punct", C.c_void_p),
+                        ("n_punct", C.c_int32), ("mod_order", C.c_int32), ("n_mod_sym", C.c_int32)]
+        self._tx_gen = None if gen is None else np.ascontiguousarray(gen, dtype=np.uint16)
+        self._tx_punct = np.ascontiguousarray(punct, dtype=np.int32)
+        t = TxDesc(None if self._tx_gen is None else self._tx_gen.ctypes.data, crc_len, random_msg, parallel,
+                   self._tx_punct.ctypes.data if self._tx_punct.size else None, self._tx_punct.size, mod_order, n_mod_sym)
+        self._tx_L = n_mod_sym
+        self.lib.nbl_set_transmitter.argtypes = [C.c_void_p, C.c_void_p]
+        self._chk(self.lib.nbl_set_transmitter(self.h, C.byref(t)))
+
+    def transmit_batch(self, slot, pn_state, lane_state, sigma):
+        pn_state = np.ascontiguousarray(pn_state, dtype=np.uint16)
+        lane_state = np.ascontiguousarray(lane_state, dtype=np.uint32)
+        self.lib.nbl_transmit_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32]
+        rc = self.lib.nbl_transmit_batch(self.h, slot, pn_state.ctypes.data, lane_state.ctypes.data, sigma, pn_state.shape[0])
+        self._chk(rc)
+
+    def read_transmitted(self, slot, b0, n):
+        """(tx_msg [n][K], tx_code [n][N], tx_index [n][L]) of lanes b0 .. b0 + n - 1 of a slot"""
+        N, K = self.code.N, self.code.N - self.code.M
+        msg = np.zeros((n, K), dtype=np.int32)
+        cw = np.zeros((n, N), dtype=np.int32)
+        txi = np.zeros((n, self._tx_L), dtype=np.uint8)
+        self.lib.nbl_read_transmitted.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.nbl_read_transmitted(self.h, slot, b0, n, msg.ctypes.data, cw.ctypes.data, txi.ctypes.data))
+        return msg, cw, txi
+
+    def read_slot_rx(self, slot, b0, n):
+        """diagnostic: the received samples [n][L][2] a slot holds"""
+        rx = np.zeros((n, self._tx_L, 2))
+        self.lib.nbl_debug_read_slot_rx.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        self._chk(self.lib.nbl_debug_read_slot_rx(self.h, slot, b0, n, rx.ctypes.data))
+        return rx
+
+    def set_decoded(self, slot, sym):
+        """diagnostic: put decoded words [B][N] where nbl_decode_batch_resident leaves a slot's outputs"""
+        sym = np.ascontiguousarray(sym, dtype=np.int32)
+        self.lib.nbl_debug_set_decoded.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        self._chk(self.lib.nbl_debug_set_decoded(self.h, slot, sym.ctypes.data, sym.shape[0]))
+
+    def count_errors(self, slot, B):
+        es = np.zeros(B, dtype=np.int32)
+        eb = np.zeros(B, dtype=np.int32)
+        ok = np.zeros(B, dtype=np.uint8)
+        self.lib.nbl_count_errors.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.nbl_count_errors(self.h, slot, B, es.ctypes.data, eb.ctypes.data, ok.ctypes.data))
+        return es, eb, ok
+
+    def encode_batch(self, msg):
+        msg = np.ascontiguousarray(msg, dtype=np.int32)
+        B = msg.shape[0]
+        cw = np.zeros((B, self.code.N), dtype=np.int32)
+        mo = np.zeros_like(msg)
+        self.lib.nbl_encode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.nbl_encode_batch(self.h, msg.ctypes.data, B, cw.ctypes.data, mo.ctypes.data))
+        return cw, mo
 
     def channel(self, tx_index, lane_state, sigma):
         """diagnostic: the received samples [B][L][2] the device-side channel forms, and the fraction of log / cos values the host's libm settled"""

@@ -69,6 +69,31 @@ struct nbl_decoder {
 	double *d_rxs[2] = {nullptr, nullptr}; // resident received samples of nbl_channel_batch, one per slot
 	size_t d_rxs_cap[2] = {0, 0};
 	int rxs_B[2] = {0, 0};
+	// device-side transmitter and error count (nbl_set_transmitter)
+	struct Tx {
+		bool on = false;
+		int crc_len = 0, random_msg = 0, K = 0, nb = 0, nw = 0, nwg = 0, mb = 0, period = 1, par_mod = 0;
+		unsigned long long *T = nullptr, *G = nullptr; // [nw][N p] PN bits -> code bits; [nwg][N p] message bits -> code bits (= T when crc_len == 0)
+		int *keep = nullptr;          // [L mb] code bit carried by every modulator bit
+		uint32_t *crc_col = nullptr;  // [K p] remainder of message bit i under CrcCheck's type-1 polynomial
+		int16_t *phase_of = nullptr;  // [2048] register state -> position in seq, -1 = all-zero output
+		uint8_t *seq = nullptr;       // [period] output bit of the register along its cycle
+		uint16_t *pn = nullptr;       // [cap] staging of pn_state
+		unsigned long long *u = nullptr; // [cap][nw]
+		uint8_t *bits = nullptr;      // [cap][N p]
+		size_t cap = 0;
+		uint8_t *code[2] = {nullptr, nullptr}, *txi[2] = {nullptr, nullptr}; // per slot: [B][N] code symbols, [B][L] constellation indices
+		size_t slot_cap[2] = {0, 0};
+		int tx_B[2] = {0, 0};
+		int *dec[2] = {nullptr, nullptr}; // per slot: outputs of the last nbl_decode_batch_resident
+		size_t dec_cap[2] = {0, 0};
+		int dec_B[2] = {0, 0};
+		int *cnt = nullptr;           // [cnt_cap] err_sym, [cnt_cap] err_bit, then [cnt_cap] bytes crc_ok
+		size_t cnt_cap = 0;
+		// nbl_encode_batch scratch (decode thread)
+		int *e_msg = nullptr; unsigned long long *e_u = nullptr; uint8_t *e_bits = nullptr, *e_code = nullptr;
+		size_t e_cap = 0;
+	} tx;
 	std::string err2;              // error text of the channel thread (nbl_channel_batch); nbl_last_error reports both
 	// hipGraph replay of the iteration loop: one executable graph per window of iterations (fixed iterations: the whole loop;
 	// early exit: the `poll_every` iterations between two polls), captured on the decoder's own stream the first time a window is
@@ -87,6 +112,8 @@ struct nbl_decoder {
 	double ms[4] = {0, 0, 0, 0};
 	long long launches[3] = {0, 0, 0};
 	int last_B = 0;
+	std::vector<int> h_coff, h_cvar, h_ch; // check-major graph and the multiplication table on the host (nbl_set_transmitter: H gen = 0)
+	std::vector<uint16_t> h_mul;
 	std::string err;
 };
 
@@ -497,6 +524,8 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 		d->osd_factor = osd->factor;
 		d->osd_acc = d->osd.flag == 0;
 	}
+	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
+	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;
 	d->all_dc4 = true;
 	for (int m = 0; m < M; m++) d->all_dc4 = d->all_dc4 && (code->chk_deg[m] == 4);
@@ -555,6 +584,8 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 	return NBL_OK;
 }
 
+static void free_transmitter(nbl_decoder *d);
+
 extern "C" void nbl_destroy(nbl_decoder *d)
 {
 	if (!d) return;
@@ -573,6 +604,7 @@ extern "C" void nbl_destroy(nbl_decoder *d)
 		if (p) (void)hipFree(p);
 	for (void *p : {(void *)d->h_fidx, (void *)d->h_farg, (void *)d->h_fval})
 		if (p) (void)hipHostFree(p);
+	free_transmitter(d);
 	for (auto &e : d->ev)
 		if (e) (void)hipEventDestroy(e);
 	if (d->h_ndone) (void)hipHostFree(d->h_ndone);
@@ -917,6 +949,7 @@ extern "C" nbl_status nbl_set_demodulator(nbl_decoder *d, const nbl_demod_desc *
 	if (dm->n_mod_sym <= 0 || (dm->mod_order == q && !dm->constellation)) return NBL_ERR_ARG;
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
+	free_transmitter(d); // its geometry repeats the demodulator's: set it again afterwards
 	const size_t nsrc = dm->mod_order == 2 ? (size_t)N * p : (size_t)N;
 	for (size_t i = 0; i < nsrc; i++)
 		if (dm->src[i] >= dm->n_mod_sym) { d->err = "demodulator source index out of range"; return NBL_ERR_ARG; }
@@ -1035,15 +1068,16 @@ static nbl_status ensure_noise(nbl_decoder *d, int B, std::string &err)
 
 // Forms RX = TX + noise for B lanes in *rx_buf (grown on demand) on stream `st`: the three kernels of nbl_noise.hip with the host's
 // libm in between.  Returns with the samples complete in HBM.
+// tx_index == NULL: the indices are already on the device, in d_txi_dev (nbl_transmit_batch).
 static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uint32_t *lane_state, double sigma, int B, hipStream_t st,
-                              double **rx_buf, size_t *rx_cap, std::string &err)
+                              double **rx_buf, size_t *rx_cap, std::string &err, const uint8_t *d_txi_dev = nullptr)
 {
 	if (!d->dm_order) { err = "nbl_set_demodulator has not been called"; return NBL_ERR_ARG; }
 	if (d->h_cons.empty() || !d->d_cons) { err = "the channel needs the constellation points (nbl_demod_desc.constellation), also for BPSK"; return NBL_ERR_ARG; }
 	nbl_status s = ensure_noise(d, B, err);
 	if (s) return s;
 	const size_t L = d->dm_L;
-	if (d->dm_order < 256) { // an index beyond the constellation would read past d_cons in the finish kernel (8 bytes per step:
+	if (tx_index && d->dm_order < 256) { // an index beyond the constellation would read past d_cons in the finish kernel (8 bytes per step:
 		// the modulation orders are powers of two, so "some byte >= order" is "some bit above the order's bits is set")
 		const size_t n = (size_t)B * L;
 		const uint8_t hi = (uint8_t)~(d->dm_order - 1);
@@ -1069,7 +1103,7 @@ static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uin
 	const double t0 = now();
 	double t1 = t0, t2 = t0, t3 = t0;
 	HIP_TRY_E(err, hipMemcpyAsync(d->d_state, lane_state, (size_t)B * 12, hipMemcpyHostToDevice, st));
-	HIP_TRY_E(err, hipMemcpyAsync(d->d_txi, tx_index, (size_t)B * L, hipMemcpyHostToDevice, st));
+	if (tx_index) HIP_TRY_E(err, hipMemcpyAsync(d->d_txi, tx_index, (size_t)B * L, hipMemcpyHostToDevice, st));
 	HIP_TRY_E(err, hipMemsetAsync(d->d_fcount, 0, 4, st));
 	HIP_TRY_E(err, nbl_launch_noise_gen(d->d_state, d->d_jump, (int)L, B, d->d_fn, d->d_fidx, d->d_farg, d->d_fcount, (unsigned)d->flag_cap, st));
 	unsigned nflag = 0;
@@ -1105,7 +1139,7 @@ static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uin
 		HIP_TRY_E(err, hipMemcpyAsync(d->d_fval, d->h_fval, (size_t)nflag * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY_E(err, nbl_launch_noise_patch(d->d_fn, d->d_fidx, d->d_fval, nflag, st));
 	}
-	HIP_TRY_E(err, nbl_launch_noise_finish(d->d_fn, d->d_txi, d->d_cons, sigma, (int)L, B, *rx_buf, st));
+	HIP_TRY_E(err, nbl_launch_noise_finish(d->d_fn, tx_index ? d->d_txi : d_txi_dev, d->d_cons, sigma, (int)L, B, *rx_buf, st));
 	HIP_TRY_E(err, hipStreamSynchronize(st));
 	if (timing)
 		fprintf(stderr, "[channel] B=%d: generate %.2f ms, list to host %.2f ms, host libm (%u values) %.2f ms, patch + finish %.2f ms\n", B,
@@ -1145,20 +1179,39 @@ extern "C" nbl_status nbl_channel_batch(nbl_decoder *d, int32_t slot, const uint
 	return s;
 }
 
+static nbl_status ensure_slot_dec(nbl_decoder *d, int slot, int B)
+{
+	const size_t need = (size_t)B * d->g.N * 4;
+	if (need <= d->tx.dec_cap[slot]) return NBL_OK;
+	if (d->tx.dec[slot]) (void)hipFree(d->tx.dec[slot]);
+	d->tx.dec[slot] = nullptr;
+	d->tx.dec_cap[slot] = 0;
+	HIP_TRY(d, hipMalloc((void **)&d->tx.dec[slot], need));
+	d->tx.dec_cap[slot] = need;
+	return NBL_OK;
+}
+
 extern "C" nbl_status nbl_decode_batch_resident(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t *out_sym, uint8_t *converged, int32_t *iters)
 {
-	if (!d || !out_sym || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0)) return NBL_ERR_ARG;
+	if (!d || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0)) return NBL_ERR_ARG;
+	if (!out_sym && !d->tx.on) { d->err = "nbl_decode_batch_resident: out_sym may only be NULL once nbl_set_transmitter has been called"; return NBL_ERR_ARG; }
 	if (d->rxs_B[slot] != B) { d->err = "nbl_decode_batch_resident: slot does not hold the samples of a batch of this size (nbl_channel_batch first)"; return NBL_ERR_ARG; }
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
 	HIP_TRY(d, nbl_launch_demod(d->d_rxs[slot], d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream));
+	if (d->tx.on) d->tx.dec_B[slot] = 0;
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
-	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
+	if (out_sym) HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
+	if (d->tx.on) { // the slot keeps its outputs for nbl_count_errors
+		if ((s = ensure_slot_dec(d, slot, B))) return s;
+		HIP_TRY(d, hipMemcpyAsync(d->tx.dec[slot], d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToDevice, d->stream));
+	}
 	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->w.done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
 	if (iters) HIP_TRY(d, hipMemcpyAsync(iters, d->w.iters, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	if (d->tx.on) d->tx.dec_B[slot] = B;
 	return NBL_OK;
 }
 
@@ -1244,5 +1297,347 @@ extern "C" nbl_status nbl_debug_osd_sums(nbl_decoder *d, int32_t b, double *out)
 	const size_t n = (size_t)d->g.N * d->g.p;
 	HIP_TRY(d, hipMemcpyAsync(out, d->osd_S + (size_t)b * n, n * 8, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	return NBL_OK;
+}
+
+// ---- transmit side and error count on the device (nbl_tx.hip) ----------------------------------------------------------------
+
+static void free_transmitter(nbl_decoder *d)
+{
+	nbl_decoder::Tx &t = d->tx;
+	if (t.G && t.G != t.T) (void)hipFree(t.G);
+	for (void *p : {(void *)t.T, (void *)t.keep, (void *)t.crc_col, (void *)t.phase_of, (void *)t.seq, (void *)t.pn, (void *)t.u, (void *)t.bits,
+	                (void *)t.code[0], (void *)t.code[1], (void *)t.txi[0], (void *)t.txi[1], (void *)t.dec[0], (void *)t.dec[1], (void *)t.cnt,
+	                (void *)t.e_msg, (void *)t.e_u, (void *)t.e_bits, (void *)t.e_code})
+		if (p) (void)hipFree(p);
+	t = nbl_decoder::Tx();
+}
+
+// one clock of the PN register (Comm.cpp:241-252): shift, then regPN[0] = regPN[10] ^ regPN[3]; the output is regPN[10] after the shift
+static inline unsigned pn_step(unsigned s) { return ((s << 1) & 2047u) | (((s >> 9) ^ (s >> 2)) & 1u); }
+
+extern "C" void nbl_pn_advance(uint16_t *state, uint64_t clocks)
+{
+	if (!state) return;
+	// the update is a map of an 11-bit state: square it repeatedly (2048-entry tables) and apply the tables of the set bits
+	static const std::vector<std::vector<uint16_t>> pow2 = [] {
+		std::vector<std::vector<uint16_t>> t(64, std::vector<uint16_t>(2048));
+		for (unsigned s = 0; s < 2048; s++) t[0][s] = (uint16_t)pn_step(s);
+		for (int k = 1; k < 64; k++)
+			for (unsigned s = 0; s < 2048; s++) t[k][s] = t[k - 1][t[k - 1][s]];
+		return t;
+	}();
+	unsigned s = *state & 2047u;
+	for (int k = 0; k < 64; k++)
+		if ((clocks >> k) & 1) s = pow2[k][s];
+	*state = (uint16_t)s;
+}
+
+// tap masks of the CRC registers (Comm.cpp:513-533): bit j set for G[j], j = 0 .. len - 1
+static uint32_t crc_tap_mask(int len, int type24)
+{
+	static const int t8[] = {0, 1, 3, 4, 7}, t16[] = {0, 5, 12}, t24a[] = {0, 1, 3, 4, 5, 6, 7, 10, 11, 14, 17, 18, 23}, t24b[] = {0, 1, 5, 6, 23};
+	uint32_t m = 0;
+	if (len == 8) for (int x : t8) m |= 1u << x;
+	else if (len == 16) for (int x : t16) m |= 1u << x;
+	else if (len == 24 && !type24) for (int x : t24a) m |= 1u << x;
+	else if (len == 24) for (int x : t24b) m |= 1u << x;
+	return m;
+}
+
+template <typename T> static nbl_status tx_upload(std::string &err, const std::vector<T> &h, T **dst)
+{
+	HIP_TRY_E(err, hipMalloc((void **)dst, h.size() * sizeof(T) + 16));
+	HIP_TRY_E(err, hipMemcpy(*dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_set_transmitter(nbl_decoder *d, const nbl_tx_desc *tx)
+{
+	if (!d || !tx) return NBL_ERR_ARG;
+	d->err.clear();
+	const int N = d->g.N, M = d->g.M, q = d->g.q, p = d->g.p, K = N - M;
+	if (!d->dm_order) { d->err = "nbl_set_transmitter: nbl_set_demodulator has not been called"; return NBL_ERR_ARG; }
+	if (d->h_cons.empty() || !d->d_cons) { d->err = "nbl_set_transmitter: the demodulator was set without constellation points (the channel needs them, also for BPSK)"; return NBL_ERR_ARG; }
+	if (tx->mod_order != d->dm_order || tx->n_mod_sym != d->dm_L) { d->err = "nbl_set_transmitter: mod_order / n_mod_sym differ from the demodulator's"; return NBL_ERR_ARG; }
+	if (tx->mod_order > 256) { d->err = "nbl_set_transmitter: mod_order above 256 is not supported (constellation indices are bytes)"; return NBL_ERR_UNSUPPORTED; }
+	if (tx->crc_len != 0 && tx->crc_len != 8 && tx->crc_len != 16 && tx->crc_len != 24) { d->err = "nbl_set_transmitter: crc_len must be 0, 8, 16 or 24"; return NBL_ERR_ARG; }
+	if (K <= 0) { d->err = "nbl_set_transmitter: the code has no message symbols"; return NBL_ERR_ARG; }
+	if (tx->crc_len > K * p) { d->err = "nbl_set_transmitter: crc_len exceeds the message length K log2(q)"; return NBL_ERR_UNSUPPORTED; }
+	if (tx->parallel < 1) { d->err = "nbl_set_transmitter: parallel < 1"; return NBL_ERR_ARG; }
+	if (tx->n_punct < 0 || (tx->n_punct > 0 && !tx->punct)) { d->err = "nbl_set_transmitter: bad puncture list"; return NBL_ERR_ARG; }
+	for (int i = 0; i < tx->n_punct; i++)
+		if (tx->punct[i] < 0 || tx->punct[i] >= N || (i > 0 && tx->punct[i] <= tx->punct[i - 1])) { d->err = "nbl_set_transmitter: punctured positions must be ascending and below N"; return NBL_ERR_ARG; }
+	const int mb = ilog2(tx->mod_order);
+	// MOD_SYM_LEN = (N - n_punct) p / MOD_BIT_PER_SYM (Comm.cpp:105): the modulator consumes the first L mb kept bits
+	if ((long long)tx->n_mod_sym * mb > (long long)(N - tx->n_punct) * p) { d->err = "nbl_set_transmitter: n_mod_sym needs more bits than the unpunctured code word has"; return NBL_ERR_ARG; }
+	if (tx->random_msg && !tx->gen) { d->err = "nbl_set_transmitter: gen is NULL with random_msg != 0"; return NBL_ERR_ARG; }
+	const int rows = N * p, nb = K * p - tx->crc_len, nw = (nb + 63) / 64, nwg = (K * p + 63) / 64;
+	if (rows > 65536 || (size_t)rows * nwg * 8 > ((size_t)64 << 20)) { d->err = "nbl_set_transmitter: code too large for the transmit kernel (N log2(q) above 65536 bits or a matrix above 64 MiB)"; return NBL_ERR_UNSUPPORTED; }
+	// H gen = 0 with the decoder's own graph and tables
+	if (tx->gen) {
+		for (size_t i = 0; i < (size_t)N * K; i++)
+			if (tx->gen[i] >= q) { d->err = "nbl_set_transmitter: gen holds a value >= q"; return NBL_ERR_ARG; }
+		for (int m = 0; m < M; m++)
+			for (int k = 0; k < K; k++) {
+				int acc = 0;
+				for (int ce = d->h_coff[m]; ce < d->h_coff[m + 1]; ce++) acc ^= d->h_mul[(size_t)d->h_ch[ce] * q + tx->gen[(size_t)d->h_cvar[ce] * K + k]];
+				if (acc) { d->err = "nbl_set_transmitter: H * gen != 0 (check " + std::to_string(m) + ", message symbol " + std::to_string(k) + ")"; return NBL_ERR_ARG; }
+			}
+	}
+	HIP_TRY(d, hipSetDevice(d->device));
+	if (d->stream2) HIP_TRY(d, hipStreamSynchronize(d->stream2));
+	free_transmitter(d);
+	nbl_decoder::Tx &t = d->tx;
+	t.crc_len = tx->crc_len; t.random_msg = tx->random_msg; t.K = K; t.nb = nb; t.nw = nw; t.nwg = nwg; t.mb = mb;
+	nbl_status st;
+	if (tx->gen) {
+		// G: code bit n p + j as a function of message bit k p + i = bit j of gen[n][k] * x^i, taken from gf_mul itself
+		std::vector<unsigned long long> G((size_t)nwg * rows, 0ull);
+		for (int n = 0; n < N; n++)
+			for (int k = 0; k < K; k++) {
+				const int h = tx->gen[(size_t)n * K + k];
+				if (!h) continue;
+				for (int i = 0; i < p; i++) {
+					const int v = d->h_mul[(size_t)h * q + (1 << i)], c = k * p + i;
+					for (int j = 0; j < p; j++)
+						if ((v >> j) & 1) G[(size_t)(c >> 6) * rows + n * p + j] |= 1ull << (c & 63);
+				}
+			}
+		if ((st = tx_upload(d->err, G, &t.G))) { free_transmitter(d); return st; }
+		if (tx->crc_len == 0) t.T = t.G;
+		else if (nb > 0) {
+			// message bits = [u ; C u]: CRCEncode (type 0) of the unit vector e_i leaves, after the remaining nb - 1 - i zero inputs,
+			// the register r_i; r_(nb-1) = taps, r_i = one zero-input clock of r_(i+1).  Parity bit c = register bit len - 1 - c.
+			const int len = tx->crc_len;
+			const uint32_t taps = crc_tap_mask(len, 0), keepm = (1u << len) - 1u;
+			std::vector<uint32_t> r(nb);
+			uint32_t reg = taps;
+			for (int i = nb - 1; i >= 0; i--) {
+				r[i] = reg;
+				const uint32_t fb = (reg >> (len - 1)) & 1u;
+				reg = ((reg << 1) & keepm) ^ (fb ? taps : 0u);
+			}
+			std::vector<unsigned long long> T((size_t)nw * rows, 0ull);
+			auto gbit = [&](int row, int c) { return (G[(size_t)(c >> 6) * rows + row] >> (c & 63)) & 1ull; };
+			for (int row = 0; row < rows; row++) {
+				// columns of G at the parity positions, as a register-shaped mask: parity bit c <-> register bit len - 1 - c
+				uint32_t pm = 0;
+				for (int c = 0; c < len; c++)
+					if (gbit(row, nb + c)) pm |= 1u << (len - 1 - c);
+				for (int i = 0; i < nb; i++) {
+					const unsigned long long b = gbit(row, i) ^ (unsigned long long)(__builtin_popcount(r[i] & pm) & 1);
+					if (b) T[(size_t)(i >> 6) * rows + row] |= 1ull << (i & 63);
+				}
+			}
+			if ((st = tx_upload(d->err, T, &t.T))) { free_transmitter(d); return st; }
+		}
+	}
+	{ // kept code bits in modulator order (Puncture, Comm.cpp:290-308)
+		std::vector<int> keep;
+		int pi = 0;
+		for (int n = 0; n < N; n++) {
+			if (pi < tx->n_punct && tx->punct[pi] == n) { pi++; continue; }
+			for (int j = 0; j < p; j++) keep.push_back(n * p + j);
+		}
+		keep.resize((size_t)tx->n_mod_sym * mb);
+		if ((st = tx_upload(d->err, keep, &t.keep))) { free_transmitter(d); return st; }
+	}
+	{ // CrcCheck (type 1 for CRC-24) of the K p decoded message bits: remainder of bit i; the last bit enters register bit 0
+		std::vector<uint32_t> col((size_t)K * p, 0u);
+		if (tx->crc_len) {
+			const int len = tx->crc_len;
+			const uint32_t taps = crc_tap_mask(len, 1), keepm = (1u << len) - 1u;
+			uint32_t reg = 1u;
+			for (int i = K * p - 1; i >= 0; i--) {
+				col[i] = reg;
+				const uint32_t fb = (reg >> (len - 1)) & 1u;
+				reg = ((reg << 1) & keepm) ^ (fb ? taps : 0u);
+			}
+		}
+		if ((st = tx_upload(d->err, col, &t.crc_col))) { free_transmitter(d); return st; }
+	}
+	{ // the register's cycle from the reference's initial contents (Comm.cpp:58-74); a state off the cycle differs from one on it
+	  // in regPN[10] only, which no output and no later state depends on
+		std::vector<int16_t> phase(2048, -1);
+		std::vector<uint8_t> seq;
+		unsigned s0 = 0;
+		static const int init[11] = {1, 0, 1, 0, 0, 0, 1, 1, 0, 0, 1};
+		for (int i = 0; i < 11; i++) s0 |= (unsigned)init[i] << i;
+		for (unsigned s = s0; phase[s] < 0; s = pn_step(s)) { phase[s] = (int16_t)seq.size(); seq.push_back((uint8_t)((s >> 9) & 1u)); }
+		for (unsigned s = 0; s < 2048; s++)
+			if (phase[s] < 0 && (s & 1023u)) {
+				const unsigned tw = s ^ 1024u;
+				if (phase[tw] >= 0) phase[s] = phase[tw];
+				else { d->err = "nbl_set_transmitter: internal error, PN register state off its cycle"; free_transmitter(d); return NBL_ERR_ARG; }
+			}
+		t.period = (int)seq.size();
+		t.par_mod = tx->parallel % t.period;
+		if ((st = tx_upload(d->err, phase, &t.phase_of)) || (st = tx_upload(d->err, seq, &t.seq))) { free_transmitter(d); return st; }
+	}
+	t.on = true;
+	return NBL_OK;
+}
+
+// per-call scratch and the slot's buffers of the channel thread
+static nbl_status ensure_tx(nbl_decoder *d, int slot, int B, std::string &err)
+{
+	nbl_decoder::Tx &t = d->tx;
+	const size_t rows = (size_t)d->g.N * d->g.p;
+	if ((size_t)B > t.cap) {
+		for (void *p : {(void *)t.pn, (void *)t.u, (void *)t.bits})
+			if (p) (void)hipFree(p);
+		t.pn = nullptr; t.u = nullptr; t.bits = nullptr; t.cap = 0;
+		HIP_TRY_E(err, hipMalloc((void **)&t.pn, (size_t)B * 2 + 16));
+		HIP_TRY_E(err, hipMalloc((void **)&t.u, (size_t)B * (t.nw > 0 ? t.nw : 1) * 8));
+		HIP_TRY_E(err, hipMalloc((void **)&t.bits, (size_t)B * rows));
+		t.cap = B;
+	}
+	if ((size_t)B > t.slot_cap[slot]) {
+		for (void *p : {(void *)t.code[slot], (void *)t.txi[slot]})
+			if (p) (void)hipFree(p);
+		t.code[slot] = nullptr; t.txi[slot] = nullptr; t.slot_cap[slot] = 0;
+		HIP_TRY_E(err, hipMalloc((void **)&t.code[slot], (size_t)B * d->g.N));
+		HIP_TRY_E(err, hipMalloc((void **)&t.txi[slot], (size_t)B * d->dm_L));
+		t.slot_cap[slot] = B;
+	}
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_transmit_batch(nbl_decoder *d, int32_t slot, const uint16_t *pn_state, const uint32_t *lane_state, double sigma, int32_t B)
+{
+	if (!d || !pn_state || !lane_state || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0)) return NBL_ERR_ARG;
+	d->err2.clear();
+	if (!d->tx.on) { d->err2 = "nbl_transmit_batch: nbl_set_transmitter has not been called"; return NBL_ERR_ARG; }
+	HIP_TRY_E(d->err2, hipSetDevice(d->device));
+	if (!d->stream2) HIP_TRY_E(d->err2, hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
+	nbl_decoder::Tx &t = d->tx;
+	d->rxs_B[slot] = 0;
+	t.tx_B[slot] = 0;
+	nbl_status s = ensure_tx(d, slot, B, d->err2);
+	if (s) return s;
+	hipStream_t st = d->stream2;
+	const int N = d->g.N, p = d->g.p, rows = N * p;
+	if (t.random_msg && t.nb > 0) {
+		HIP_TRY_E(d->err2, hipMemcpyAsync(t.pn, pn_state, (size_t)B * 2, hipMemcpyHostToDevice, st));
+		HIP_TRY_E(d->err2, nbl_launch_tx_pn(t.pn, t.phase_of, t.seq, t.period, t.par_mod, t.nb, t.nw, B, t.u, st));
+		HIP_TRY_E(d->err2, nbl_launch_tx_encode(t.T, t.u, rows, t.nw, B, t.bits, st));
+	} else {
+		HIP_TRY_E(d->err2, hipMemsetAsync(t.bits, 0, (size_t)B * rows, st)); // all-zero message and code word, encoder skipped (Comm.cpp:258-268)
+	}
+	HIP_TRY_E(d->err2, nbl_launch_tx_pack(t.bits, t.keep, N, p, d->dm_L, t.mb, B, t.code[slot], t.txi[slot], st));
+	s = run_channel(d, nullptr, lane_state, sigma, B, st, &d->d_rxs[slot], &d->d_rxs_cap[slot], d->err2, t.txi[slot]);
+	if (s == NBL_OK) { d->rxs_B[slot] = B; t.tx_B[slot] = B; }
+	return s;
+}
+
+extern "C" nbl_status nbl_count_errors(nbl_decoder *d, int32_t slot, int32_t B, int32_t *err_sym, int32_t *err_bit, uint8_t *crc_ok)
+{
+	if (!d || B <= 0 || slot < 0 || slot > 1 || !err_sym || !err_bit || !crc_ok) return NBL_ERR_ARG;
+	d->err.clear();
+	nbl_decoder::Tx &t = d->tx;
+	if (!t.on) { d->err = "nbl_count_errors: nbl_set_transmitter has not been called"; return NBL_ERR_ARG; }
+	if (t.tx_B[slot] != B) { d->err = "nbl_count_errors: slot does not hold a transmitted batch of this size (nbl_transmit_batch first)"; return NBL_ERR_ARG; }
+	if (t.dec_B[slot] != B) { d->err = "nbl_count_errors: slot does not hold the outputs of a decode of this size (nbl_decode_batch_resident first)"; return NBL_ERR_ARG; }
+	HIP_TRY(d, hipSetDevice(d->device));
+	if ((size_t)B > t.cnt_cap) {
+		if (t.cnt) (void)hipFree(t.cnt);
+		t.cnt = nullptr; t.cnt_cap = 0;
+		HIP_TRY(d, hipMalloc((void **)&t.cnt, (size_t)B * 9 + 16));
+		t.cnt_cap = B;
+	}
+	int *es = t.cnt, *eb = t.cnt + t.cnt_cap;
+	uint8_t *ok = (uint8_t *)(t.cnt + 2 * t.cnt_cap);
+	HIP_TRY(d, nbl_launch_tx_errcount(t.dec[slot], t.code[slot], t.crc_col, d->g.N, t.K, d->g.p, t.crc_len, B, es, eb, ok, d->stream));
+	HIP_TRY(d, hipMemcpyAsync(err_sym, es, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipMemcpyAsync(err_bit, eb, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipMemcpyAsync(crc_ok, ok, (size_t)B, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_encode_batch(nbl_decoder *d, const int32_t *msg, int32_t B, int32_t *code, int32_t *msg_out)
+{
+	if (!d || !msg || !code || B < 0) return NBL_ERR_ARG;
+	d->err.clear();
+	nbl_decoder::Tx &t = d->tx;
+	if (!t.on || !t.G) { d->err = "nbl_encode_batch: nbl_set_transmitter has not been called with a generator"; return NBL_ERR_ARG; }
+	if (B == 0) return NBL_OK;
+	const int N = d->g.N, p = d->g.p, K = t.K, rows = N * p, q = d->g.q;
+	for (size_t i = 0; i < (size_t)B * K; i++)
+		if (msg[i] < 0 || msg[i] >= q) { d->err = "nbl_encode_batch: message symbol outside 0 .. q - 1"; return NBL_ERR_ARG; }
+	HIP_TRY(d, hipSetDevice(d->device));
+	const int chunk = B < 4096 ? B : 4096;
+	if ((size_t)chunk > t.e_cap) {
+		for (void *x : {(void *)t.e_msg, (void *)t.e_u, (void *)t.e_bits, (void *)t.e_code})
+			if (x) (void)hipFree(x);
+		t.e_msg = nullptr; t.e_u = nullptr; t.e_bits = nullptr; t.e_code = nullptr; t.e_cap = 0;
+		HIP_TRY(d, hipMalloc((void **)&t.e_msg, (size_t)chunk * K * 4));
+		HIP_TRY(d, hipMalloc((void **)&t.e_u, (size_t)chunk * t.nwg * 8));
+		HIP_TRY(d, hipMalloc((void **)&t.e_bits, (size_t)chunk * rows));
+		HIP_TRY(d, hipMalloc((void **)&t.e_code, (size_t)chunk * N));
+		t.e_cap = chunk;
+	}
+	std::vector<uint8_t> h((size_t)chunk * N);
+	for (int b0 = 0; b0 < B; b0 += chunk) {
+		const int n = B - b0 < chunk ? B - b0 : chunk;
+		HIP_TRY(d, hipMemcpyAsync(t.e_msg, msg + (size_t)b0 * K, (size_t)n * K * 4, hipMemcpyHostToDevice, d->stream));
+		HIP_TRY(d, nbl_launch_tx_msgbits(t.e_msg, K, p, t.nwg, n, t.e_u, d->stream));
+		HIP_TRY(d, nbl_launch_tx_encode(t.G, t.e_u, rows, t.nwg, n, t.e_bits, d->stream));
+		// (symbols only: the index output goes to the same buffer's tail-less twin with L = 0)
+		HIP_TRY(d, nbl_launch_tx_pack(t.e_bits, t.keep, N, p, 0, t.mb, n, t.e_code, nullptr, d->stream));
+		HIP_TRY(d, hipMemcpyAsync(h.data(), t.e_code, (size_t)n * N, hipMemcpyDeviceToHost, d->stream));
+		HIP_TRY(d, hipStreamSynchronize(d->stream));
+		for (int b = 0; b < n; b++) {
+			for (int i = 0; i < N; i++) code[(size_t)(b0 + b) * N + i] = h[(size_t)b * N + i];
+			if (msg_out) for (int i = 0; i < K; i++) msg_out[(size_t)(b0 + b) * K + i] = h[(size_t)b * N + i];
+		}
+	}
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_read_transmitted(nbl_decoder *d, int32_t slot, int32_t b0, int32_t n, int32_t *tx_msg, int32_t *tx_code, uint8_t *tx_index)
+{
+	if (!d || slot < 0 || slot > 1 || b0 < 0 || n < 0) return NBL_ERR_ARG;
+	d->err.clear();
+	nbl_decoder::Tx &t = d->tx;
+	if (!t.on || t.tx_B[slot] <= 0 || (long long)b0 + n > t.tx_B[slot]) { d->err = "nbl_read_transmitted: the slot does not hold these lanes (nbl_transmit_batch first)"; return NBL_ERR_ARG; }
+	if (n == 0) return NBL_OK;
+	HIP_TRY(d, hipSetDevice(d->device));
+	const int N = d->g.N, K = t.K, L = d->dm_L;
+	if (tx_msg || tx_code) {
+		std::vector<uint8_t> h((size_t)n * N);
+		HIP_TRY(d, hipMemcpy(h.data(), t.code[slot] + (size_t)b0 * N, h.size(), hipMemcpyDeviceToHost));
+		for (int b = 0; b < n; b++) {
+			if (tx_code) for (int i = 0; i < N; i++) tx_code[(size_t)b * N + i] = h[(size_t)b * N + i];
+			if (tx_msg) for (int i = 0; i < K; i++) tx_msg[(size_t)b * K + i] = h[(size_t)b * N + i];
+		}
+	}
+	if (tx_index) HIP_TRY(d, hipMemcpy(tx_index, t.txi[slot] + (size_t)b0 * L, (size_t)n * L, hipMemcpyDeviceToHost));
+	return NBL_OK;
+}
+
+// Diagnostic only (not part of include/nbldpc.h): the received samples [n][L][2] a slot holds
+extern "C" nbl_status nbl_debug_read_slot_rx(nbl_decoder *d, int32_t slot, int32_t b0, int32_t n, double *rx)
+{
+	if (!d || slot < 0 || slot > 1 || b0 < 0 || n <= 0 || !rx || b0 + n > d->rxs_B[slot]) return NBL_ERR_ARG;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	HIP_TRY(d, hipMemcpy(rx, d->d_rxs[slot] + (size_t)b0 * d->dm_L * 2, (size_t)n * d->dm_L * 16, hipMemcpyDeviceToHost));
+	return NBL_OK;
+}
+
+// Diagnostic only (not part of include/nbldpc.h): put decoded words [B][N] where nbl_decode_batch_resident leaves a slot's outputs
+extern "C" nbl_status nbl_debug_set_decoded(nbl_decoder *d, int32_t slot, const int32_t *sym, int32_t B)
+{
+	if (!d || slot < 0 || slot > 1 || !sym || B <= 0) return NBL_ERR_ARG;
+	d->err.clear();
+	if (!d->tx.on) { d->err = "nbl_debug_set_decoded: nbl_set_transmitter has not been called"; return NBL_ERR_ARG; }
+	HIP_TRY(d, hipSetDevice(d->device));
+	d->tx.dec_B[slot] = 0;
+	nbl_status s = ensure_slot_dec(d, slot, B);
+	if (s) return s;
+	HIP_TRY(d, hipMemcpy(d->tx.dec[slot], sym, (size_t)B * d->g.N * 4, hipMemcpyHostToDevice));
+	d->tx.dec_B[slot] = B;
 	return NBL_OK;
 }

@@ -59,3 +59,13 @@ hipError_t nbl_launch_noise_gen(const uint32_t *state, const uint32_t *jump, int
                                 unsigned *flag_count, unsigned cap, hipStream_t st);
 hipError_t nbl_launch_noise_patch(double *fn, const uint32_t *flag_idx, const double *val, unsigned n, hipStream_t st);
 hipError_t nbl_launch_noise_finish(const double *fn, const uint8_t *tx_index, const double *cons, double sigma, int L, int B, double *rx, hipStream_t st);
+
+// transmit chain and error count on the device (nbl_tx.hip).  T is word-major: T[w * rows + r] = columns 64 w .. 64 w + 63 of row r.
+#define NBL_TX_F 8 // frames a thread of the encode kernel carries (their packed inputs sit in LDS: NBL_TX_F * nw * 8 bytes)
+hipError_t nbl_launch_tx_pn(const uint16_t *pn_state, const int16_t *phase_of, const uint8_t *seq, int period, int par_mod, int nb, int nw,
+                            int B, unsigned long long *u, hipStream_t st);
+hipError_t nbl_launch_tx_encode(const unsigned long long *T, const unsigned long long *u, int rows, int nw, int B, uint8_t *bits, hipStream_t st);
+hipError_t nbl_launch_tx_pack(const uint8_t *bits, const int *keep, int N, int p, int L, int mb, int B, uint8_t *code, uint8_t *txi, hipStream_t st);
+hipError_t nbl_launch_tx_msgbits(const int *msg, int K, int p, int nw, int B, unsigned long long *u, hipStream_t st);
+hipError_t nbl_launch_tx_errcount(const int *dec, const uint8_t *code, const uint32_t *crc_col, int N, int K, int p, int crc_len, int B,
+                                  int *err_sym, int *err_bit, uint8_t *crc_ok, hipStream_t st);

@@ -124,6 +124,71 @@ int nblh_simulate(const char *profile, int device, double *rows, int max_rows)
 	return n;
 }
 
+// the encoder of a profile's code as a dense map gen [N][K] (CNBLDPC::Generator); no GPU
+int nblh_generator(const char *profile, unsigned short *gen_out)
+{
+	CSimulation sim;
+	if (sim.Initial(profile) != 0) return -1;
+	CNBLDPC code;
+	if (!code.Initial(sim, -1)) return -2;
+	std::vector<uint16_t> gen;
+	if (!code.Generator(gen)) return -3;
+	memcpy(gen_out, gen.data(), gen.size() * sizeof(uint16_t));
+	return 0;
+}
+
+// TakeDecoded + ErrCount of the host chain (Comm.cpp:421-493) for `count` frames: tx_msg [count][K] the transmitted message symbols
+// as Encode left them, decoded [count][N] -> err_sym, err_bit, crc_ok per frame.  No GPU.
+int nblh_err_count(const char *profile, const int *tx_msg, const int *decoded, int count, int *err_sym, int *err_bit, int *crc_ok)
+{
+	CSimulation sim;
+	if (sim.Initial(profile) != 0) return -1;
+	CNBLDPC code;
+	if (!code.Initial(sim, -1)) return -2;
+	CComm c;
+	if (!c.Initial(sim, 0, &code)) return -3;
+	const int N = code.CodeLen, K = N - code.ChkLen, p = c.Bit_Len_PerSYM;
+	for (int f = 0; f < count; f++) {
+		for (int s = 0; s < K; s++) {
+			c.TX_MSG_SYM[s] = tx_msg[(size_t)f * K + s];
+			for (int k = 0; k < p; k++) c.TX_MSG_BIT[s * p + k] = (c.TX_MSG_SYM[s] >> k) & 1;
+		}
+		c.TakeDecoded(decoded + (size_t)f * N, true);
+		double es = 0, eb = 0;
+		int ok = 0;
+		c.ErrCount(-1, es, eb, ok);
+		err_sym[f] = (int)es; err_bit[f] = (int)eb; crc_ok[f] = ok;
+	}
+	return 0;
+}
+
+// CComm::CRCEncode on n bits (one int each): out [n + len]
+int nblh_crc_encode(const int *in, int n, int len, int type24, int *out)
+{
+	CComm c;
+	c.CRCEncode(out, in, n, len, type24);
+	return 0;
+}
+
+// the PN register clocked literally: `clocks` calls of CComm::GenPN from `state` (bit i = regPN[i]); returns the register
+int nblh_pn_clock(int state, unsigned long long clocks)
+{
+	CComm c;
+	c.pn = state & 2047;
+	for (unsigned long long i = 0; i < clocks; i++) c.GenPN();
+	return c.pn;
+}
+
+// each lane's PN register in front of its first frame at an Eb/N0 point (ResetSources: the initial contents advanced `lane` clocks)
+int nblh_pn_initial(int lane)
+{
+	CComm c;
+	CSimulation sim;
+	sim.parallel = 1;
+	c.SetEbN0(sim, lane);
+	return c.pn;
+}
+
 // encoder check: encode `count` random messages, return 0 if every codeword satisfies every parity check
 int nblh_encode(const char *profile, const int *msg, int count, int *code_out)
 {

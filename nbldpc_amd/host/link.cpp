@@ -35,6 +35,8 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 	if (const char *e = getenv("NBL_DEVICE_DEMOD")) device_demod = atoi(e) != 0;
 	if (const char *e = getenv("NBL_DEVICE_NOISE")) device_noise = atoi(e) != 0;
 	if (!device_demod || lanes[0]->CONSTELLATION.size() > 256) device_noise = false;
+	if (const char *e = getenv("NBL_DEVICE_TX")) device_tx = atoi(e) != 0;
+	if (device_tx && !device_noise) { error = "NBL_DEVICE_TX=1 needs the device-side channel (NBL_DEVICE_NOISE / NBL_DEVICE_DEMOD on, at most 256 constellation points)"; return false; }
 	if (const char *e = getenv("NBL_PIPELINE")) pipeline = atoi(e) != 0;
 	if (const char *e = getenv("NBL_HOST_THREADS")) host_threads = atoi(e);
 	else { // 16 threads keep one GPU fed; more GPUs decode more lanes per cycle
@@ -53,9 +55,29 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 		for (auto &x : extra)
 			if (x->SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data()) != 0) { error = x->LastError(); return false; }
 	}
+	if (device_tx) {
+		CComm &l0 = *lanes[0];
+		std::vector<uint16_t> gen;
+		if (sim.randomMsg && !code.Generator(gen)) { error = code.LastError(); return false; }
+		const uint16_t *g = sim.randomMsg ? gen.data() : nullptr;
+		if (code.SetTransmitter(g, sim.crcLen, sim.randomMsg, sim.parallel, l0.modOrder, l0.MOD_SYM_LEN) != 0) { error = code.LastError(); return false; }
+		for (auto &x : extra)
+			if (x->SetTransmitter(g, sim.crcLen, sim.randomMsg, sim.parallel, l0.modOrder, l0.MOD_SYM_LEN) != 0) { error = x->LastError(); return false; }
+		// one frame moves a lane's PN register (K p - crcLen) * parallel clocks (none with an all-zero message) and its generator
+		// 4 L draws: both are fixed maps, tabulated once with the library's helpers
+		const uint64_t clocks = sim.randomMsg ? (uint64_t)(l0.MSG_BIT_LEN - l0.crcLen) * (uint64_t)sim.parallel : 0;
+		pn_frame.resize(2048);
+		for (int s = 0; s < 2048; s++) { pn_frame[s] = (uint16_t)s; nbl_pn_advance(&pn_frame[s], clocks); }
+		uint32_t one[3] = {1, 1, 1};
+		nbl_rand_advance(one, 4ull * (uint64_t)l0.MOD_SYM_LEN);
+		for (int k = 0; k < 3; k++) rs_frame[k] = one[k];
+		pn_cur.assign(sim.parallel, 0);
+		rs_cur.assign((size_t)3 * sim.parallel, 0);
+	}
 	for (int slot = 0; slot < (pipeline ? 2 : 1); slot++) {
+		if (device_tx) pn_batch[slot].assign(sim.parallel, 0);
 		rx_batch[slot].assign(device_demod && !device_noise ? (size_t)2 * lanes[0]->MOD_SYM_LEN * sim.parallel : 0, 0.0);
-		txi_batch[slot].assign(device_noise ? (size_t)lanes[0]->MOD_SYM_LEN * sim.parallel : 0, 0);
+		txi_batch[slot].assign(device_noise && !device_tx ? (size_t)lanes[0]->MOD_SYM_LEN * sim.parallel : 0, 0);
 		state_batch[slot].assign(device_noise ? (size_t)3 * sim.parallel : 0, 0);
 		L_batch[slot].assign(device_demod ? 0 : per * sim.parallel, 0.0);
 	}
@@ -77,6 +99,13 @@ void CLink::BeginSNR()
 {
 	sim.ClearSimuCount();
 	for (int i = 0; i < sim.parallel; i++) lanes[i]->SetEbN0(sim, i);
+	if (device_tx)
+		for (int i = 0; i < sim.parallel; i++) {
+			pn_cur[i] = (uint16_t)lanes[i]->pn;
+			rs_cur[(size_t)3 * i] = (unsigned int)(lanes[i]->Rand.IX % 61967ul);
+			rs_cur[(size_t)3 * i + 1] = (unsigned int)(lanes[i]->Rand.IY % 63443ul);
+			rs_cur[(size_t)3 * i + 2] = (unsigned int)(lanes[i]->Rand.IZ % 63599ul);
+		}
 }
 
 template <class F> static void over_lanes(int P, int T, F work)
@@ -91,6 +120,17 @@ template <class F> static void over_lanes(int P, int T, F work)
 // (main.cpp:46); results do not depend on the thread count
 void CLink::FrontEnds(int slot)
 {
+	if (device_tx) { // the lanes' state bookkeeping is all the host does
+		static const unsigned int mod[3] = {61967u, 63443u, 63599u};
+		memcpy(pn_batch[slot].data(), pn_cur.data(), sizeof(uint16_t) * pn_cur.size());
+		memcpy(state_batch[slot].data(), rs_cur.data(), sizeof(unsigned int) * rs_cur.size());
+		for (int i = 0; i < sim.parallel; i++) {
+			pn_cur[i] = pn_frame[pn_cur[i] & 2047];
+			for (int k = 0; k < 3; k++) rs_cur[(size_t)3 * i + k] = (unsigned int)((unsigned long long)rs_cur[(size_t)3 * i + k] * rs_frame[k] % mod[k]);
+		}
+		channel_ok[slot] = Transmit(slot);
+		return;
+	}
 	const size_t per = (size_t)code.CodeLen * (code.GFq - 1);
 	over_lanes(sim.parallel, host_threads, [&](int lo, int hi) {
 		for (int i = lo; i < hi; i++) {
@@ -138,6 +178,27 @@ bool CLink::Channel(int slot)
 	return true;
 }
 
+bool CLink::Transmit(int slot)
+{
+	const int P = sim.parallel, G = (int)devices.size();
+	const double sigma = lanes[0]->sigma_n;
+	std::vector<int> rc(G, 0);
+	auto shard = [&](int gidx) {
+		const int lo = (int)((long long)P * gidx / G), hi = (int)((long long)P * (gidx + 1) / G);
+		CNBLDPC &dec = gidx == 0 ? code : *extra[gidx - 1];
+		if (hi > lo) rc[gidx] = dec.TransmitBatch(slot, &pn_batch[slot][lo], &state_batch[slot][(size_t)3 * lo], sigma, hi - lo);
+	};
+	if (G == 1) shard(0);
+	else {
+		std::vector<std::thread> th;
+		for (int gidx = 0; gidx < G; gidx++) th.emplace_back(shard, gidx);
+		for (auto &x : th) x.join();
+	}
+	for (int gidx = 0; gidx < G; gidx++)
+		if (rc[gidx] != 0) { error = (gidx == 0 ? code : *extra[gidx - 1]).LastError(); return false; }
+	return true;
+}
+
 bool CLink::Decode(int slot)
 {
 	if (device_noise && !channel_ok[slot]) return false;
@@ -151,7 +212,7 @@ bool CLink::Decode(int slot)
 		const int lo = (int)((long long)P * gidx / G), hi = (int)((long long)P * (gidx + 1) / G);
 		CNBLDPC &dec = gidx == 0 ? code : *extra[gidx - 1];
 		if (hi > lo && device_noise)
-			rc[gidx] = dec.DecodingBatchResident(slot, sigma, hi - lo, &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo]);
+			rc[gidx] = dec.DecodingBatchResident(slot, sigma, hi - lo, device_tx ? nullptr : &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo]);
 		else if (hi > lo)
 			rc[gidx] = device_demod
 			    ? dec.DecodingBatchSamples(&rx_batch[slot][rxper * lo], sigma, hi - lo, &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo])
@@ -175,6 +236,17 @@ void CLink::CountErrors(int slot)
 	const int P = sim.parallel;
 	std::vector<double> es(P), eb(P);
 	std::vector<int> ok(P);
+	if (device_tx) { // counted where the decoded words are; only the three counters per lane come back
+		const int G = (int)devices.size();
+		std::vector<int> esi(P), ebi(P);
+		std::vector<uint8_t> ok8(P);
+		for (int gidx = 0; gidx < G; gidx++) {
+			const int lo = (int)((long long)P * gidx / G), hi = (int)((long long)P * (gidx + 1) / G);
+			CNBLDPC &dec = gidx == 0 ? code : *extra[gidx - 1];
+			if (hi > lo && dec.CountErrors(slot, hi - lo, &esi[lo], &ebi[lo], &ok8[lo]) != 0) { error = dec.LastError(); count_ok = false; return; }
+		}
+		for (int i = 0; i < P; i++) { es[i] = esi[i]; eb[i] = ebi[i]; ok[i] = ok8[i]; }
+	} else
 	over_lanes(P, host_threads, [&](int lo, int hi) {
 		for (int i = lo; i < hi; i++) {
 			lanes[i]->TakeDecoded(&out_batch[(size_t)code.CodeLen * i], conv[i] != 0);
@@ -196,6 +268,7 @@ bool CLink::Cycle()
 	if (!Decode(0)) return false;
 	const double t2 = now_s();
 	CountErrors(0);
+	if (!count_ok) return false;
 	t_front += t1 - t0;
 	t_decode += t2 - t1;
 	t_err += now_s() - t2;
@@ -229,6 +302,7 @@ bool CLink::RunPoint(bool verbose)
 		const double t2 = now_s();
 		if (!ok) return false;
 		CountErrors(slot);
+		if (!count_ok) return false;
 		t_front += t1 - t0;   // host time that ran under the decode
 		t_decode += t2 - t1;  // decode time NOT hidden by the front-end
 		t_err += now_s() - t2;

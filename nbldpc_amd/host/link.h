@@ -20,6 +20,15 @@ public:
 	                                   // NBL_DEVICE_NOISE=0 draws the noise on the host threads.  Needs device_demod.
 	std::vector<unsigned char> txi_batch[2]; // [parallel][MOD_SYM_LEN] constellation indices
 	std::vector<unsigned int> state_batch[2]; // [parallel][3] generator states in front of the frame
+	bool device_tx = false;            // NBL_DEVICE_TX=1: message source, CRC, encoder, puncturing and modulator on the GPU as well, and the
+	                                   // error count after the decode; the host keeps each lane's PN register and generator state only.
+	                                   // Needs device_noise; the same frames, bit for bit, as the host chain.
+	std::vector<uint16_t> pn_cur, pn_batch[2]; // [parallel] PN register of every lane: now / in front of the slot's frame
+	std::vector<unsigned int> rs_cur;  // [parallel][3] generator state of every lane now
+	std::vector<uint16_t> pn_frame;    // register state -> state one frame later
+	unsigned int rs_frame[3] = {1, 1, 1}; // multipliers of one frame's 4 L uniform draws
+	bool Transmit(int slot);           // device-side transmit chain + channel of the slot's frames
+	bool count_ok = true;
 	bool channel_ok[2] = {true, true};
 	bool Channel(int slot);            // device-side channel of the slot's frames (runs under the previous cycle's decode)
 	bool pipeline = true;              // NBL_PIPELINE=0: strictly serial cycles

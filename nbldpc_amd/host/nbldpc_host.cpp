@@ -159,6 +159,46 @@ int CNBLDPC::Encode(int *msg_sym, int *code_sym) // NBLDPC.cpp:562-604
 	return 0;
 }
 
+bool CNBLDPC::Generator(std::vector<uint16_t> &gen)
+{
+	const int N = CodeLen, K = CodeLen - ChkLen;
+	if (enc_link.empty() && !InitialEncode()) return false;
+	gen.assign((size_t)N * K, 0);
+	std::vector<int> msg(K), cw(N);
+	for (int k = 0; k < K; k++) {
+		std::fill(msg.begin(), msg.end(), 0);
+		msg[k] = 1;
+		Encode(msg.data(), cw.data());
+		for (int n = 0; n < N; n++) gen[(size_t)n * K + k] = (uint16_t)cw[n];
+	}
+	return true;
+}
+
+int CNBLDPC::SetTransmitter(const uint16_t *gen, int crc_len, int random_msg, int parallel, int mod_order, int n_mod_sym)
+{
+	if (!dec) { error = "decoder not initialised"; return -1; }
+	nbl_tx_desc tx = {gen, crc_len, random_msg, parallel, PuncturePositionV.data(), PunctureLen, mod_order, n_mod_sym};
+	nbl_status st = nbl_set_transmitter(dec, &tx);
+	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
+	return 0;
+}
+
+int CNBLDPC::TransmitBatch(int slot, const uint16_t *pn_state, const unsigned int *lane_state, double sigma, int B)
+{
+	if (!dec) { error = "decoder not initialised"; return -1; }
+	nbl_status st = nbl_transmit_batch(dec, slot, pn_state, lane_state, sigma, B);
+	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
+	return 0;
+}
+
+int CNBLDPC::CountErrors(int slot, int B, int *err_sym, int *err_bit, uint8_t *crc_ok)
+{
+	if (!dec) { error = "decoder not initialised"; return -1; }
+	nbl_status st = nbl_count_errors(dec, slot, B, err_sym, err_bit, crc_ok);
+	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
+	return 0;
+}
+
 int CNBLDPC::DecodingBatch(const double *L_ch, int B, int *out, uint8_t *converged, int *iters)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }

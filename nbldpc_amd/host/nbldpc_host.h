@@ -45,6 +45,13 @@ public:
 	// the same in two phases (slot 0 / 1): the channel of cycle k+1 may run while cycle k is decoded
 	int ChannelBatch(int slot, const unsigned char *tx_index, const unsigned int *lane_state, double sigma, int B);
 	int DecodingBatchResident(int slot, double sigma, int B, int *out, uint8_t *converged, int *iters);
+	// the encoder as a dense linear map, gen [CodeLen][K]: code[n] = sum_k gen[n][k] * msg[k] (K unit encodes; Encode is GF(q)-linear),
+	// the final column exchanges included.  Builds the encoder first if the profile did not ask for one (Random Msg: 0).
+	bool Generator(std::vector<uint16_t> &gen);
+	// device-side transmit chain and error count (include/nbldpc.h: nbl_set_transmitter / nbl_transmit_batch / nbl_count_errors)
+	int SetTransmitter(const uint16_t *gen, int crc_len, int random_msg, int parallel, int mod_order, int n_mod_sym);
+	int TransmitBatch(int slot, const uint16_t *pn_state, const unsigned int *lane_state, double sigma, int B);
+	int CountErrors(int slot, int B, int *err_sym, int *err_bit, uint8_t *crc_ok);
 	const std::string &LastError() const { return error; }
 	nbl_decoder *Handle() const { return dec; }
 

@@ -27,6 +27,13 @@ def load():
         L.nblh_channel.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.nblh_simulate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int]
         L.nblh_encode.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.nblh_generator.argtypes = [C.c_char_p, C.c_void_p]
+        L.nblh_err_count.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nblh_crc_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.nblh_pn_clock.argtypes = [C.c_int, C.c_ulonglong]
+        L.nblh_pn_initial.argtypes = [C.c_int]
+        L.nbl_pn_advance.argtypes = [C.c_void_p, C.c_uint64]  # (libnbldpc_hip.so's helper, reachable through this library's link)
+        L.nbl_pn_advance.restype = None
         _lib = L
     return _lib
 
@@ -99,3 +106,51 @@ def encode(workdir_path, msgs, N):
     if rc != 0:
         raise RuntimeError(f"nblh_encode rc={rc}")
     return out
+
+
+def generator(workdir_path, N, K):
+    """The encoder of the profile's code as a dense map gen [N][K] uint16: code[n] = sum_k gen[n][k] * msg[k] over GF(q).  No GPU."""
+    gen = np.zeros((N, K), dtype=np.uint16)
+    with workdir(workdir_path):
+        rc = load().nblh_generator(b"NBLDPC.Profile.txt", gen.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"nblh_generator rc={rc}")
+    return gen
+
+
+def err_count(workdir_path, tx_msg, decoded):
+    """TakeDecoded + ErrCount of the host chain per frame: (err_sym, err_bit, crc_ok), int32 [B] each.  No GPU."""
+    tx_msg = np.ascontiguousarray(tx_msg, dtype=np.int32)
+    decoded = np.ascontiguousarray(decoded, dtype=np.int32)
+    B = decoded.shape[0]
+    es, eb, ok = (np.zeros(B, dtype=np.int32) for _ in range(3))
+    with workdir(workdir_path):
+        rc = load().nblh_err_count(b"NBLDPC.Profile.txt", tx_msg.ctypes.data, decoded.ctypes.data, B, es.ctypes.data, eb.ctypes.data, ok.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"nblh_err_count rc={rc}")
+    return es, eb, ok
+
+
+def crc_encode(bits, crc_len, type24=0):
+    """CComm::CRCEncode: the bits followed by their crc_len parity bits (type24: which of the two CRC-24 polynomials)"""
+    bits = np.ascontiguousarray(bits, dtype=np.int32)
+    out = np.zeros(bits.size + crc_len, dtype=np.int32)
+    load().nblh_crc_encode(bits.ctypes.data, bits.size, crc_len, type24, out.ctypes.data)
+    return out
+
+
+def pn_clock(state, clocks):
+    """the PN register after `clocks` literal calls of CComm::GenPN"""
+    return load().nblh_pn_clock(int(state), int(clocks))
+
+
+def pn_initial(lane):
+    """PN register of `lane` in front of its first frame of an Eb/N0 point"""
+    return load().nblh_pn_initial(int(lane))
+
+
+def pn_advance(state, clocks):
+    """nbl_pn_advance of the C ABI (pure host arithmetic)"""
+    s = np.array([state], dtype=np.uint16)
+    load().nbl_pn_advance(s.ctypes.data, int(clocks))
+    return int(s[0])

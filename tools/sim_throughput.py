@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """End-to-end rate of the harness (nbldpc_sim): link-chain front-end on the host + batched decode on the GPU + error count.
 
-usage: python tools/sim_throughput.py [cfg3|cfg2|cfg4|cfg1|ems16|tems16] [parallel] [cycles] [ebn0]
+usage: python tools/sim_throughput.py [--tx=0|1|both] [--runs=N] [cfg3|cfg2|cfg4|cfg1|ems16|tems16] [parallel] [cycles] [ebn0]
 Runs the driver in a scratch directory for `cycles` simulation cycles (stop rule on the frame count only), prints its phase summary.
+--tx sets NBL_DEVICE_TX for the run (1: message source, CRC, encoder, puncturing, modulator and error count on the GPU); `both` runs
+the two modes alternately, --runs times each, so that one command times them on the same box.
 NBL_DEVICE_DEMOD=0 builds the symbol LLRs on the host instead of shipping received samples; NBL_HOST_THREADS sets the front-end threads.
 """
 import os
@@ -25,18 +27,29 @@ CFG = {
 
 
 def main():
-    name = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
-    P = int(sys.argv[2]) if len(sys.argv) > 2 else 16384
-    cycles = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
+    argv = [sys.argv[0]] + [a for a in sys.argv[1:] if not a.startswith("--")]
+    opt = dict(f[2:].split("=", 1) for f in flags)
+    modes = {"0": ["0"], "1": ["1"], "both": ["0", "1"]}[opt["tx"]] if "tx" in opt else [None]
+    runs = int(opt.get("runs", 1))
+    name = argv[1] if len(argv) > 1 else "cfg3"
+    P = int(argv[2]) if len(argv) > 2 else 16384
+    cycles = int(argv[3]) if len(argv) > 3 else 3
     code, cons, kw = CFG[name]
-    ebn0 = float(sys.argv[4]) if len(sys.argv) > 4 else 1.5
+    ebn0 = float(argv[4]) if len(argv) > 4 else 1.5
     with tempfile.TemporaryDirectory() as td:
         hostlib.prepare_workdir(td, dict(code=code, parallel=P, snr_begin=ebn0, snr_step=1.0, snr_stop=ebn0, constellation=cons,
                                          min_err_frame=-1, min_uerr_frame=-1, min_sim_cycle=(cycles - 1) * P, seed=173, **kw), code, cons)
         exe = os.path.join(ROOT, "nbldpc_amd", "host", "nbldpc_sim")
-        r = subprocess.run([exe], cwd=td, capture_output=True, text=True)
-        print(r.stdout[-600:])
-        print(r.stderr[-600:])
+        for _ in range(runs):
+            for tx in modes:
+                env = dict(os.environ)
+                if tx is not None:
+                    env["NBL_DEVICE_TX"] = tx
+                    print(f"--- {name} P={P} cycles={cycles} Eb/N0={ebn0} NBL_DEVICE_TX={tx}")
+                r = subprocess.run([exe], cwd=td, capture_output=True, text=True, env=env)
+                print(r.stdout[-600:])
+                print(r.stderr[-600:])
 
 
 if __name__ == "__main__":
