@@ -81,8 +81,13 @@ typedef struct nbl_params {
 typedef struct nbl_decoder nbl_decoder;
 
 /* gf_mul: q*q multiplication table, gf_inv: q inverses (gf_inv[0] ignored) -- the tables CGF::Initial loads
- * from ./SRC/Arith.Table.GF.<q>.txt (GF.cpp:81-113).  Addition must be XOR (checked against gf_mul's
- * distributivity is not attempted; the reference's tables are polynomial-basis for every q it ships).
+ * from ./SRC/Arith.Table.GF.<q>.txt (GF.cpp:81-113).  Addition is XOR: the table must be that of GF(2)[x] / m(x) in the
+ * polynomial basis for an irreducible m of degree p (q = 2^p), any of them -- m need not be primitive, nor the one the reference
+ * ships for this q.  The irreducible polynomial is recovered from the table (q | gf_mul[2][q/2]) and the tables are checked in
+ * full at creation, before anything is indexed by one of their entries and before the device is touched: every gf_mul entry
+ * below q, row and column 0 zero, every gf_mul[a][b] the shift-and-XOR product modulo m, and for every a in 1 .. q-1
+ * gf_inv[a] < q with gf_mul[a][gf_inv[a]] == 1 (which no reducible m can meet).  Anything else is NBL_ERR_ARG, the message
+ * names the first offending entry.
  * Shapes: q = 4 .. 256 (a power of two), check and variable degrees up to 8, ems_nm <= q, T-EMS with p * (largest check
  * degree) <= 32 (q = 2^p; the path code of TEMS_ConstructConf in 32 bits); anything else is NBL_ERR_UNSUPPORTED / NBL_ERR_ARG
  * with a message, at creation, never at the first decode. */
@@ -118,7 +123,8 @@ nbl_status nbl_create_ex(const nbl_code_desc *code, const uint16_t *gf_mul, cons
  *             elimination never ends)
  *   gf_mat    [q][p][p] bytes, gf_mat[e][l][k] = GFElement[e].ValueMatric[l][k]: the binary image of "multiply by e" as the caller's
  *             loader left it.  The reference's loader (GF.cpp:137) reads q-2 of the q-1 matrices, so alpha^(q-2)'s stays zero; pass
- *             the same to reproduce it, or the full set for the true binary image.
+ *             the same to reproduce it, or the full set for the true binary image.  The matrix of element 1 must be the identity
+ *             (NBL_ERR_ARG otherwise); the layout lists powers of x, so a loader fills it for a primitive modulus only.
  * The binary matrix [crc_rows; H_bit] ((crc_rows + M p) rows of N p bits, q = 2^p) is built and checked once, at creation, before
  * any device call: N p above NBL_OSD_MAX_BITS (the matrix and the candidate codewords live in one workgroup's LDS; every shipped
  * code fits) and a matrix without full row rank (the reference's elimination never ends on one) are NBL_ERR_UNSUPPORTED.

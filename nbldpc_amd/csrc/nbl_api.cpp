@@ -362,6 +362,56 @@ static int gf2_rank(std::vector<std::vector<uint64_t>> m, int nw)
 	return rank;
 }
 
+// The caller's field tables, checked in full before anything is indexed by one of their entries: gf_mul must be THE table of
+// GF(2)[x] / poly in the polynomial basis (poly read off x * x^(p-1)), gf_inv its inverses.  Some kernels multiply by shift and
+// XOR with poly, others look gf_mul up as bytes or through offsets built from it: they decode the same code only if the whole
+// table is that product.  Every non-zero element has an inverse exactly when poly is irreducible, so a reducible modulus is
+// refused by the last condition.  Returns poly, or 0 with the first offending entry named in `msg`.
+static int validate_field(int q, const uint16_t *gf_mul, const uint16_t *gf_inv, std::string &msg)
+{
+	const int p = ilog2(q);
+	for (int a = 0; a < q; a++)
+		for (int b = 0; b < q; b++)
+			if (gf_mul[(size_t)a * q + b] >= q) {
+				msg = "gf_mul[" + std::to_string(a) + "][" + std::to_string(b) + "] = " + std::to_string(gf_mul[(size_t)a * q + b]) + " is not an element of GF(" + std::to_string(q) + ")";
+				return 0;
+			}
+	for (int a = 0; a < q; a++)
+		if (gf_mul[a] != 0 || gf_mul[(size_t)a * q] != 0) {
+			const bool row = gf_mul[a] != 0;
+			msg = "gf_mul[" + std::to_string(row ? 0 : a) + "][" + std::to_string(row ? a : 0) + "] is not zero";
+			return 0;
+		}
+	// x * x^(p-1) = x^p = poly - q
+	const int poly = q | gf_mul[(size_t)2 * q + (q >> 1)];
+	for (int a = 1; a < q; a++)
+		for (int b = 1; b < q; b++) {
+			int acc = 0, x = a;
+			for (int i = 0; i < p; i++) {
+				if ((b >> i) & 1) acc ^= x;
+				x <<= 1;
+				if (x & q) x ^= poly;
+			}
+			if (gf_mul[(size_t)a * q + b] != acc) {
+				msg = "gf_mul is not a polynomial-basis GF(2^p) table: gf_mul[" + std::to_string(a) + "][" + std::to_string(b) + "] = " + std::to_string(gf_mul[(size_t)a * q + b]) +
+				      ", the product modulo " + std::to_string(poly) + " is " + std::to_string(acc);
+				return 0;
+			}
+		}
+	for (int a = 1; a < q; a++) {
+		if (gf_inv[a] >= q) {
+			msg = "gf_inv[" + std::to_string(a) + "] = " + std::to_string(gf_inv[a]) + " is not an element of GF(" + std::to_string(q) + ")";
+			return 0;
+		}
+		if (gf_mul[(size_t)a * q + gf_inv[a]] != 1) {
+			msg = "gf_inv inconsistent with gf_mul: gf_mul[" + std::to_string(a) + "][gf_inv[" + std::to_string(a) + "] = " + std::to_string(gf_inv[a]) + "] is not 1 (modulus " +
+			      std::to_string(poly) + "; a reducible modulus has elements without an inverse)";
+			return 0;
+		}
+	}
+	return poly;
+}
+
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
 {
@@ -372,6 +422,9 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 	if (N <= 0 || M <= 0 || q < 4 || (q & (q - 1))) return fail_create(nullptr, NBL_ERR_ARG, "N, M must be positive and q a power of two, at least 4");
 	// (the reference ships arithmetic tables up to GF(512) but no code above GF(256); a valid request this library cannot serve)
 	if (q > 256) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "fields above GF(256) are not supported (one wave holds at most 4 symbols per lane)");
+	std::string field_err;
+	const int poly = validate_field(q, gf_mul, gf_inv, field_err);
+	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
 	switch (params->method) {
 	case NBL_METHOD_EMS: case NBL_METHOD_BP: case NBL_METHOD_TEMS: break;
 	case NBL_METHOD_BS_TEMS:
@@ -390,6 +443,9 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 		if (osd->order < -1) return fail_create(nullptr, NBL_ERR_ARG, "OSD: order < -1");
 		if (osd->flag != 0 && osd->flag != 1) return fail_create(nullptr, NBL_ERR_ARG, "OSD: flag must be 0 or 1");
 		if (!osd->gf_mat) return fail_create(nullptr, NBL_ERR_ARG, "OSD: gf_mat is NULL");
+		for (int p1 = ilog2(q), i = 0; i < p1 * p1; i++) // the matrix of "multiply by 1"
+			if (osd->gf_mat[(size_t)p1 * p1 + i] != (i / p1 == i % p1))
+				return fail_create(nullptr, NBL_ERR_ARG, "OSD: gf_mat of element 1 is not the identity (entry [" + std::to_string(i / p1) + "][" + std::to_string(i % p1) + "])");
 		if (osd->crc_rows < 0 || osd->crc_rows > osd->crc_len) return fail_create(nullptr, NBL_ERR_ARG, "OSD: crc_rows must be in 0 .. crc_len");
 		if (osd->crc_rows > 0 && osd->crc_len != 8 && osd->crc_len != 16 && osd->crc_len != 24)
 			return fail_create(nullptr, NBL_ERR_ARG, "OSD: CRC rows need crc_len 8, 16 or 24 (the reference's CRC generator is empty otherwise and its elimination never ends)");
@@ -458,7 +514,6 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 		c_var[ce] = n;
 		c_h[ce] = h;
 		c_hinv[ce] = gf_inv[h];
-		if (gf_mul[(size_t)h * q + gf_inv[h]] != 1) return fail_create(nullptr, NBL_ERR_ARG, "gf_inv inconsistent with gf_mul");
 	}
 	for (int n = 0; n < N; n++)
 		for (int e = voff[n]; e < voff[n + 1]; e++) {
@@ -485,13 +540,6 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 		const bool special = q == 256 && maxdc == 4 && params->ems_nc >= 1 && params->ems_nm <= 64;
 		if (!special && lds > 160 * 1024)
 			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
-	}
-	// primitive polynomial recovered from the table: x * x^(p-1) = x^p = poly - q
-	const int poly = q | gf_mul[(size_t)2 * q + (q >> 1)];
-	for (int a = 0; a < q; a++) {
-		int expect = (a << 1);
-		if (expect & q) expect ^= poly;
-		if (gf_mul[(size_t)a * q + 2] != expect) return fail_create(nullptr, NBL_ERR_ARG, "gf_mul is not a polynomial-basis GF(2^p) table");
 	}
 
 	int ndev = 0;

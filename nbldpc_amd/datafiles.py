@@ -7,6 +7,7 @@
 The code and constellation definitions come from nbldpc_amd/data/*.json (imported once from the reference's
 data files by tools/import_reference_data.py); the GF tables are GENERATED here from the primitive polynomial.
 """
+import functools
 import json
 import os
 
@@ -66,10 +67,47 @@ def write_constellation_file(name, path):
     return path
 
 
-def gf_tables(q):
-    """(mul[q][q], inv[q]) of GF(q) in the polynomial basis of PRIMITIVE_POLY[q]; add is XOR."""
-    poly = PRIMITIVE_POLY[q]
+def _mul_x(a, q, poly):
+    """a * x modulo `poly` (degree log2(q)), by shift and XOR"""
+    a <<= 1
+    return a ^ poly if a & q else a
+
+
+@functools.lru_cache(maxsize=None)
+def _irreducible(q):
     p = q.bit_length() - 1
+    assert 4 <= q <= 256 and 1 << p == q, q
+
+    def rem(a, d):
+        n = d.bit_length()
+        while a.bit_length() >= n:
+            a ^= d << (a.bit_length() - n)
+        return a
+    return tuple(f for f in range(q, 2 * q) if all(rem(f, d) for d in range(2, 1 << (p // 2 + 1))))
+
+
+def irreducible_polys(q):
+    """Every irreducible polynomial of degree log2(q) over GF(2) as an integer (bit i = coefficient of x^i), ascending; q <= 256.
+    Trial division by every polynomial of degree 1 .. log2(q) / 2, done once per q."""
+    return list(_irreducible(q))
+
+
+def is_primitive(q, poly):
+    """True where `poly` is irreducible of degree log2(q) and x generates the multiplicative group of GF(2)[x] / poly."""
+    if poly not in _irreducible(q):
+        return False
+    x, n = 2, 1
+    while x != 1:
+        x, n = _mul_x(x, q, poly), n + 1
+    return n == q - 1
+
+
+def gf_tables(q, poly=None):
+    """(mul[q][q], inv[q]) of GF(q) in the polynomial basis of `poly` (default PRIMITIVE_POLY[q]); add is XOR.  Any irreducible
+    polynomial of degree log2(q) gives a field; the Mat.Repr layout of gf_matrices / write_gf_tables needs a primitive one."""
+    poly = PRIMITIVE_POLY[q] if poly is None else poly
+    p = q.bit_length() - 1
+    assert poly >> p == 1, (q, poly)
     mul = [[0] * q for _ in range(q)]
     inv = [0] * q
     for a in range(q):
@@ -87,12 +125,13 @@ def gf_tables(q):
     return mul, inv
 
 
-def gf_matrices(q, as_loaded=True):
+def gf_matrices(q, as_loaded=True, poly=None):
     """[q][p][p] uint8: GFElement[e].ValueMatric of every element e, the binary image of "multiply by e" (row i of alpha^k's
     matrix holds the bits of alpha^(k+i), the Mat.Repr.GF.<q>.txt layout).  as_loaded=True: as CGF::Initial leaves them -- it reads
     q-2 of the q-1 non-zero elements (GF.cpp:137), so alpha^(q-2)'s matrix stays zero; False: the full set."""
     import numpy as np
-    mul, _ = gf_tables(q)
+    assert poly is None or is_primitive(q, poly), (q, poly, "the powers of x must reach every non-zero element")
+    mul, _ = gf_tables(q, poly)
     p = q.bit_length() - 1
     m = np.zeros((q, p, p), dtype=np.uint8)
     x = 1
@@ -105,11 +144,13 @@ def gf_matrices(q, as_loaded=True):
     return m
 
 
-def write_gf_tables(q, src_dir):
-    """Write Arith.Table.GF.<q>.txt and Mat.Repr.GF.<q>.txt under src_dir (the reference expects ./SRC/)."""
+def write_gf_tables(q, src_dir, poly=None):
+    """Write Arith.Table.GF.<q>.txt and Mat.Repr.GF.<q>.txt under src_dir (the reference expects ./SRC/).  With a modulus that
+    is irreducible but not primitive the arithmetic table is a field table all the same; the powers of x listed in Mat.Repr then
+    repeat before they reach every element, so that file serves OSD only with a primitive modulus."""
     os.makedirs(src_dir, exist_ok=True)
-    mul, inv = gf_tables(q)
-    poly = PRIMITIVE_POLY[q]
+    poly = PRIMITIVE_POLY[q] if poly is None else poly
+    mul, inv = gf_tables(q, poly)
     p = q.bit_length() - 1
     with open(os.path.join(src_dir, f"Arith.Table.GF.{q}.txt"), "w") as f:
         f.write(f"GF({q}) with Primitive Polynomial: {poly}. \nMultiply Table:\n")

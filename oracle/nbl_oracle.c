@@ -89,6 +89,9 @@ int nblo_gf_load(nblo_gf *gf, int q, const char *path)
 	}
 	if (fscanf(f, "%63s %63s", w1, w2) != 2) goto bad;
 	for (int i = 0; i < q; i++) if (fscanf(f, "%d", &gf->inv[i]) != 1) goto bad;
+	/* the modulus of the loaded table, not the default one gf_alloc put there: x * x^(p-1) = x^p = poly - q.  (No decoder reads
+	 * gf->poly -- they go through mul / inv alone -- but the struct must not name a polynomial the table was not made from.) */
+	gf->poly = q | gf->mul[2 * q + (q >> 1)];
 	fclose(f);
 	return 0;
 bad:

@@ -61,7 +61,7 @@ def dump(name, parallel, frames, ebn0):
     points = ls.points_of(name)
     kw = ls.profile_of(name, parallel)
     tmp = tempfile.mkdtemp(prefix="golden_")
-    prof = prepare_spec_workdir(tmp, kw, spec, points, absolute=True)
+    prof = prepare_spec_workdir(tmp, kw, spec, points, absolute=True, poly=ls.poly_of(name))
     subprocess.check_call([DRIVER, "dump", prof, tmp, repr(ebn0), str(frames), "1", ""], cwd=tmp, stderr=subprocess.DEVNULL,
                           stdout=subprocess.DEVNULL, timeout=600)
     arrs = {k: np.load(os.path.join(tmp, k + ".npy")) for k in ("tx_code", "tx_msg", "sigma", "L_ch")}
@@ -73,6 +73,8 @@ def run_shape(name):
     t0 = time.time()
     arrs, kw, spec, points = dump(name, LANES, FRAMES, EBN0)
     meta = dict(shape=name, profile=kw, spec=spec, points=points.tolist(), ebn0=EBN0, frames=FRAMES, reference_flags=FLAGS)
+    if ls.poly_of(name) is not None:   # the GF tables of the work directory were written with this modulus
+        meta["poly"] = ls.poly_of(name)
     path = os.path.join(GOLD, f"link_shape_{name}.npz")
     save_npz(path, meta=json.dumps(meta), **arrs)
     print(f"link_shape_{name}: N={spec['N']} B={arrs['tx_code'].shape[0]} ({time.time() - t0:.1f}s, {os.path.getsize(path) / 1e3:.0f} kB)", flush=True)

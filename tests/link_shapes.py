@@ -24,7 +24,8 @@ from degree_util import degree_code
 SEEDS = range(9300, 13300)
 
 # id -> q, M, check-degree cycle, variable-degree cycle, seed, crc_len, nqam (2 or q; default 2), punct (degree whose variables are
-# punctured, default 0 = none) and `expect`: the properties the shape is in the table for.  exch = number of column exchanges of the
+# punctured, default 0 = none), poly (the modulus the GF tables of the work directory and of the decoder are made from, default: the
+# one of nbldpc_amd/datafiles.py::PRIMITIVE_POLY) and `expect`: the properties the shape is in the table for.  exch = number of column exchanges of the
 # encoder, exch_msg / exch_parity = how many of them reach a column below K (then gen[:K] is not the identity) / at or above K.
 SHAPES = {
     # GF(4), N p < 64: one partial wave of encode rows, nw = 1, L < 64.  The smallest shape: lane strides and the encode chunks run on it
@@ -64,7 +65,13 @@ SHAPES = {
     "qary_gf128": dict(q=128, M=8, chk=(3,), var=(2,), seed=9300, crc_len=8, nqam=128, expect=dict(N=12, L=12)),
     # BPSK with punctured symbols 0, N - 1 and two adjacent ones (the degree-3 variables)
     "punct_ends": dict(q=16, M=10, chk=(4, 5), var=(2, 2, 2, 3), seed=9321, crc_len=8, punct=3, expect=dict(punct_ends=1)),
+    # another field representation: tables, generator matrix and the reference's own chain all made with a primitive polynomial that
+    # is not the default one (19 -> 25, 67 -> 91), BPSK and one point per symbol.  The GF(16) graph's encoder exchanges a message
+    # column, so gen[:K] holds products of the alternative table
+    "gf16_m25": dict(q=16, M=12, chk=(4,), var=(2,), seed=9300, crc_len=8, poly=25, expect=dict(N=24, exch_msg_min=1)),
+    "qary_gf64_m91": dict(q=64, M=8, chk=(3,), var=(2,), seed=9300, crc_len=8, nqam=64, poly=91, expect=dict(N=12, L=12)),
 }
+FIELD_SHAPES = ("gf16_m25", "qary_gf64_m91")
 # shapes the compiled reference cannot run (module docstring): the host chain is held to the reference on every other shape, and on
 # these the GPU tests compare with the host chain alone
 NO_REFERENCE = ("k1",)
@@ -93,18 +100,19 @@ def stride_cases():
     return {"period_minus_1": T - 1, "period": T, "period_plus_1": T + 1, "twice_period": 2 * T}
 
 
-def gf_np(q):
+@functools.lru_cache(maxsize=None)
+def gf_np(q, poly=None):
     import nbldpc_amd.datafiles as df
-    mul, inv = df.gf_tables(q)
+    mul, inv = df.gf_tables(q, poly)
     return np.array(mul, dtype=np.int64), np.array(inv, dtype=np.int64)
 
 
-def initial_encode(spec):
+def initial_encode(spec, poly=None):
     """CNBLDPC::InitialEncode restated: Gauss elimination from the last row up with the pivot of row r in column r + K; a missing
     pivot is fetched from a row above, else from the nearest column to the left that has an entry in this row (the exchange is
     recorded).  Returns the recorded exchanges [(col, left), ..] in the order they were made, or None where no pivot is found."""
     N, M, q = spec["N"], spec["M"], spec["q"]
-    mul, inv = gf_np(q)
+    mul, inv = gf_np(q, poly)
     H = np.zeros((M, N), dtype=np.int64)
     for m, row in enumerate(spec["chk_rows"]):
         for v, h in row:
@@ -156,7 +164,7 @@ def describe(name, code, spec):
     punct = [n for n in range(N) if s.get("punct", 0) and int(code.var_deg[n]) == s["punct"]]
     mb = order.bit_length() - 1
     nb = K * p - s["crc_len"]
-    swaps = initial_encode(spec)
+    swaps = initial_encode(spec, s.get("poly"))
     # no check holds two punctured variables: every punctured symbol (channel LLR 0) has a check that determines it
     alone = all(sum(v - 1 in punct for v, _ in row) <= 1 for row in spec["chk_rows"])
     return dict(punct_alone=int(alone), q=q, N=N, M=M, K=K, p=p, Np=N * p, nb=nb, nw=(nb + 63) // 64, crc_len=s["crc_len"], order=order, punct=punct,
@@ -181,9 +189,10 @@ def meets(name, info):
     return out
 
 
-def reference_can_initialise(code):
+def reference_can_initialise(code, poly=None):
+    import nbldpc_amd.datafiles as df
     from osd_shapes import full_rank
-    return full_rank(code, 8, 0)
+    return full_rank(code, 8, 0, gf_mat=None if poly is None else df.gf_matrices(code.q, poly=poly))
 
 
 @functools.lru_cache(maxsize=None)
@@ -197,8 +206,13 @@ def shape(name):
     for key, (got, want, ok) in meets(name, info).items():
         assert ok, (name, key, got, want)
     assert info["K"] >= 1 and 0 <= info["nb"] and info["order"] in (2, s["q"]), (name, info)
-    assert reference_can_initialise(code), (name, "bit-level H is not of full row rank")
+    assert reference_can_initialise(code, s.get("poly")), (name, "bit-level H is not of full row rank")
     return code, spec, info
+
+
+def poly_of(name):
+    """the modulus of a shape's field, None for the default one"""
+    return SHAPES[name].get("poly")
 
 
 def profile_of(name, parallel, **over):
@@ -233,7 +247,7 @@ if __name__ == "__main__":
                 print(name, seed, "no graph:", e)
                 break
             info = describe(name, code, spec)
-            if info["swaps"] is None or not all(ok for _, _, ok in meets(name, info).values()) or not reference_can_initialise(code):
+            if info["swaps"] is None or not all(ok for _, _, ok in meets(name, info).values()) or not reference_can_initialise(code, SHAPES[name].get("poly")):
                 continue
             found = seed
             break

@@ -19,13 +19,14 @@ def write_points_file(points, path):
     return path
 
 
-def prepare_spec_workdir(path, profile_kwargs, spec, points, absolute=False):
+def prepare_spec_workdir(path, profile_kwargs, spec, points, absolute=False, poly=None):
     """hostlib.prepare_workdir for a graph spec and a point table: SRC/ with the GF tables, code.txt, constellation.txt and
-    NBLDPC.Profile.txt.  absolute: the profile names the two files by their full paths."""
+    NBLDPC.Profile.txt.  absolute: the profile names the two files by their full paths.  poly: the modulus of the GF tables (None:
+    the default one)."""
     from degree_util import write_spec_code_file
     from nbldpc_amd.profiles import profile_text
     os.makedirs(path, exist_ok=True)
-    df.write_gf_tables(spec["q"], os.path.join(path, "SRC"))
+    df.write_gf_tables(spec["q"], os.path.join(path, "SRC"), poly)
     write_spec_code_file(spec, os.path.join(path, "code.txt"))
     write_points_file(points, os.path.join(path, "constellation.txt"))
     kw = dict(profile_kwargs)
@@ -39,9 +40,11 @@ def prepare_spec_workdir(path, profile_kwargs, spec, points, absolute=False):
 
 class Link:
     """Work directory of a profile, the geometry CComm::Initial derives from it, and a decoder with demodulator and transmitter set.
-    spec / points: a graph spec (tests/degree_util.py) and a constellation table in place of the shipped code_name / cons."""
+    spec / points: a graph spec (tests/degree_util.py) and a constellation table in place of the shipped code_name / cons.  poly: the
+    modulus of the field -- the tables of the work directory (from which the host encoder derives `gen`) and those handed to
+    nbl_create are made from it."""
 
-    def __init__(self, tmp_path, profile, code_name, cons, P, max_batch=0, with_tx=True, spec=None, points=None):
+    def __init__(self, tmp_path, profile, code_name, cons, P, max_batch=0, with_tx=True, spec=None, points=None, poly=None):
         from nbldpc_amd.profiles import DEFAULTS
         self.dir = str(tmp_path)
         self.prof = dict(DEFAULTS)
@@ -54,7 +57,7 @@ class Link:
             self.points = np.array([[x[1], x[2]] for x in sorted(df.constellations()[cons])])
             self.code = nb.Code(code_name)
         else:
-            prepare_spec_workdir(self.dir, kw, spec, points)
+            prepare_spec_workdir(self.dir, kw, spec, points, poly=poly)
             c = spec
             self.points = np.ascontiguousarray(points, dtype=np.float64)
             self.code = nb.Code(spec=spec)
@@ -74,7 +77,10 @@ class Link:
                 src.append(k if keep else -1)
                 k += keep
         self.src = np.array(src, dtype=np.int32)
-        self.dec = nb.Decoder(self.code, self.prof["method"], self.prof["max_iter"], max_batch=max_batch, poll_every=2, **decoder_kwargs(self.prof))
+        assert poly is None or spec is not None
+        self.gf = None if poly is None else tuple(np.array(t, dtype=np.int64) for t in df.gf_tables(self.q, poly))
+        self.dec = nb.Decoder(self.code, self.prof["method"], self.prof["max_iter"], max_batch=max_batch, poll_every=2, gf=self.gf,
+                              **decoder_kwargs(self.prof))
         self.dec.set_demodulator(self.order, self.L, self.src, self.points)
         self.gen = hostlib.generator(self.dir, self.N, self.K) if self.prof["random_msg"] else None
         if with_tx:

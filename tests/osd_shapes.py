@@ -140,8 +140,8 @@ def gf2_rank(A):
     return rank
 
 
-def full_rank(code, crc_len=8, crc_rows=0):
-    A = osd_matrix(code, crc_len, crc_rows)
+def full_rank(code, crc_len=8, crc_rows=0, gf_mat=None):
+    A = osd_matrix(code, crc_len, crc_rows, gf_mat)
     return A.shape[0] < A.shape[1] and gf2_rank(A) == A.shape[0]
 
 
@@ -177,12 +177,14 @@ def shape(name):
     return code, edges, spec, info
 
 
-def zero_block_variables(code):
+def zero_block_variables(code, gf_mat=None):
     """Variables whose every edge carries alpha^(q-2), the coefficient whose matrix the loader leaves at zero: their columns of
     H_bit are zero, so the elimination rotates the order when it meets one of them first."""
     import nbldpc_amd as nb
-    gm = nb.datafiles.gf_matrices(code.q)
+    gm = nb.datafiles.gf_matrices(code.q) if gf_mat is None else gf_mat
     zero = [h for h in range(1, code.q) if not gm[h].any()]
+    if gf_mat is not None and not zero:      # the full set of matrices: no element has a zero block
+        return []
     assert len(zero) == 1
     out, e = [], 0
     for i in range(code.N):

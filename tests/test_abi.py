@@ -217,3 +217,74 @@ def test_create_refuses_ems_shapes_above_160_kb_of_lds():
     with pytest.raises(nb.NblError) as e:                             # nm above q
         _create(_ring_code(256, 12, 8), method=nb.METHOD_EMS, max_iter=5, ems_nm=257, ems_nc=6)
     assert e.value.status == -1 and "EMS_Nm is too large" in str(e.value)
+
+
+def test_create_validates_the_field_tables():
+    """nbl_create checks the caller's gf_mul / gf_inv in full, before anything is indexed by one of their entries and before the
+    device is touched: every refusal below is NBL_ERR_ARG on a box without a GPU too, and its message names the offending entry.
+    (Some kernels multiply by shift and XOR with the modulus recovered from the table, others look the table up as bytes: a table
+    that is right in one column only would make them decode two different codes.)  None of these tables ever reaches a kernel."""
+    import field_util as fu
+    ems = dict(method=nb.METHOD_EMS, max_iter=5, ems_nm=4, ems_nc=2)
+
+    def refused(code, mul, inv, *words):
+        with pytest.raises(nb.NblError) as e:
+            _create(code, gf=(mul, inv), **ems)
+        assert e.value.status == -1, str(e.value)
+        for w in words:
+            assert w in str(e.value), (w, str(e.value))
+
+    def tables(q, poly=None):
+        mul, inv = nb.datafiles.gf_tables(q, poly)
+        return np.array(mul, dtype=np.uint16), np.array(inv, dtype=np.uint16)
+
+    code = _ring_code(16, 8, 4)
+    mul, inv = tables(16)
+    _accepted(code, gf=(mul, inv), **ems)
+    bad = mul.copy(); bad[5, 9] = 16                                   # an entry >= q
+    refused(code, bad, inv, "gf_mul[5][9]", "not an element")
+    bad = mul.copy(); bad[3, 4], bad[3, 5] = mul[3, 5], mul[3, 4]      # two swapped entries in row 3 (column 2 untouched)
+    refused(code, bad, inv, "gf_mul[3][4]", "not a polynomial-basis")
+    bad = mul.copy(); bad[7, 11] = mul[7, 12]                          # not symmetric (bad[11][7] is still right)
+    assert bad[11, 7] != bad[7, 11]
+    refused(code, bad, inv, "gf_mul[7][11]", "not a polynomial-basis")
+    bad = mul.copy(); bad[0, 6] = 1                                    # non-zero row 0
+    refused(code, bad, inv, "gf_mul[0][6]", "not zero")
+    bad = mul.copy(); bad[6, 0] = 1                                    # .. and column 0
+    refused(code, bad, inv, "gf_mul[6][0]", "not zero")
+    # the table of a reducible modulus: 21 = (x^2 + x + 1)^2.  It IS the shift-and-XOR product modulo 21; x^2 + x + 1 = 7 has no inverse
+    rmul = np.zeros((16, 16), dtype=np.uint16)
+    for a in range(16):
+        for b in range(16):
+            acc, x = 0, a
+            for i in range(4):
+                if (b >> i) & 1:
+                    acc ^= x
+                x <<= 1
+                if x & 16:
+                    x ^= 21
+            rmul[a, b] = acc
+    assert not (rmul[7] == 1).any() and 21 not in nb.datafiles.irreducible_polys(16)
+    rinv = np.array([next((b for b in range(16) if rmul[a, b] == 1), 0) for a in range(16)], dtype=np.uint16)
+    refused(code, rmul, rinv, "gf_inv", "gf_mul[7]", "modulus 21")     # 7: the first element without an inverse
+    bad = inv.copy(); bad[9] = 16                                      # gf_inv[a] >= q
+    refused(code, mul, bad, "gf_inv[9]", "not an element")
+    # a wrong gf_inv at an element that labels no edge
+    unused = [a for a in range(1, 16) if a not in set(code.chk_h.tolist())]
+    assert unused, "every element labels an edge"
+    bad = inv.copy(); bad[unused[0]] = inv[unused[0]] ^ 1 or 2
+    refused(code, mul, bad, f"gf_inv[{unused[0]}]", "inconsistent")
+    # GF(256): a correct entry plus 256 truncates to the right byte
+    code256 = _ring_code(256, 8, 4)
+    mul, inv = tables(256)
+    _accepted(code256, gf=(mul, inv), **ems)
+    bad = mul.copy(); bad[200, 100] += 256
+    assert np.array_equal(bad.astype(np.uint8), mul.astype(np.uint8))
+    refused(code256, bad, inv, "gf_mul[200][100]", "not an element")
+    bad = inv.copy(); bad[255] += 256
+    refused(code256, mul, bad, "gf_inv[255]", "not an element")
+    # every field case is accepted: NBL_ERR_NO_DEVICE on a box without a GPU, not NBL_ERR_ARG
+    for q, poly, _ in fu.CASES:
+        for which in ("ring", "all"):
+            c, _, _ = fu.graph(which, q, poly, "ems")
+            _accepted(c, gf=fu.field(q, poly).tables, **ems)

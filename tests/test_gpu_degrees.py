@@ -75,14 +75,15 @@ def bp_frames(rng, N, q):
     return L
 
 
-def reference(oracle, checker, code, edges, meth, iters, L, kw, mode, fixed=0):
+def reference(oracle, checker, code, edges, meth, iters, L, kw, mode, fixed=0, gf=None):
     """[(flag, decisions, iterations, (post, v2c, c2v))] per frame: BS-TEMS from tests/bstems_check.cpp, the rest from the oracle.
-    mode: 'canonical' | 'literal'."""
+    mode: 'canonical' | 'literal'.  gf: a tests/field_util.py::Field (its tables for the checker, its loaded table file for the
+    oracle); None: the field of the default polynomial."""
     if meth == nb.METHOD_BS_TEMS:
         out, ret, its, st = run_checker(checker, code, L, iters, BS_CANONICAL if mode == "canonical" else BS_LITERAL, fixed_iters=fixed,
-                                        state=range(L.shape[0]), **kw)
+                                        state=range(L.shape[0]), gf=None if gf is None else gf.tables, **kw)
         return [(int(ret[b]), out[b].copy(), int(its[b]), st[b]) for b in range(L.shape[0])]
-    od = oracle.Decoder(oracle.Code(edges=edges), oracle.GF(code.q), meth, iters, oracle.CANONICAL if mode == "canonical" else oracle.LITERAL,
+    od = oracle.Decoder(oracle.Code(edges=edges), oracle.GF(code.q) if gf is None else gf.oracle_gf(oracle), meth, iters, oracle.CANONICAL if mode == "canonical" else oracle.LITERAL,
                         fixed_iters=fixed, **kw)
     ref = []
     for b in range(L.shape[0]):
@@ -91,12 +92,13 @@ def reference(oracle, checker, code, edges, meth, iters, L, kw, mode, fixed=0):
     return ref
 
 
-def gpu_equals(code, meth, iters, L, kw, refs, exact, tag, variants=(0, 1, 2), fixed=0):
+def gpu_equals(code, meth, iters, L, kw, refs, exact, tag, variants=(0, 1, 2), fixed=0, gf=None):
     """Decode L in every kernel variant; decisions, flags, iteration counts and the message state of every frame against each
     reference in `refs`.  (v2c of a codeword that converged at iteration k >= 2 is not compared unless iterations are fixed:
-    include/nbldpc.h, nbl_read_state -- the variable-node pass has already written iteration k's messages.)"""
+    include/nbldpc.h, nbl_read_state -- the variable-node pass has already written iteration k's messages.)
+    gf: the Field whose tables nbl_create gets (None: the default polynomial's)."""
     for variant in variants:
-        dec = nb.Decoder(code, meth, iters, fixed_iters=fixed, **kw)
+        dec = nb.Decoder(code, meth, iters, fixed_iters=fixed, gf=None if gf is None else gf.tables, **kw)
         _force_generic(dec, variant)
         dec.record_state(True)
         out, conv, its = dec.decode(L)

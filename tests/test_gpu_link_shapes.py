@@ -35,7 +35,7 @@ def fixture(name):
 def link(tmp_path, name, P, **kw):
     over = kw.pop("over", {})
     _, spec, info = ls.shape(name)
-    ln = Link(tmp_path, ls.profile_of(name, P, **over), None, None, P, spec=spec, points=ls.points_of(name), **kw)
+    ln = Link(tmp_path, ls.profile_of(name, P, **over), None, None, P, spec=spec, points=ls.points_of(name), poly=ls.poly_of(name), **kw)
     assert (ln.L, ln.punct, ln.K, ln.p, ln.order) == (info["L"], info["punct"], info["K"], info["p"], info["order"])
     return ln, info
 
@@ -222,6 +222,27 @@ def test_fer_with_the_device_transmitter(tmp_path, monkeypatch, name):
     for got, ref in zip(rows, a["points"]):
         for k in KEYS:
             assert got[k] == ref[k], (name, k, got, ref)
+
+
+@pytest.mark.parametrize("name", ls.FIELD_SHAPES)
+def test_generator_of_another_field_is_refused_by_the_default_table(tmp_path, name):
+    """gen derived by the host encoder from the tables of the shape's modulus: nbl_set_transmitter's H * gen = 0 check passes on a
+    decoder created with those tables and fails (NBL_ERR_ARG, on the host, before any kernel) on one created with the default
+    tables -- the check multiplies with the decoder's own field."""
+    from conftest import decoder_kwargs
+    ln, info = link(tmp_path / "a", name, 2, with_tx=False)
+    assert ln.gf is not None and not np.array_equal(ln.gf[0], ls.gf_np(ln.q)[0])
+    ln.set_tx()                                                           # the shape's own field: accepted
+    # the generator of the same graph under the default tables is another matrix
+    prepare_spec_workdir(str(tmp_path / "b"), ls.profile_of(name, 2), ls.shape(name)[1], ls.points_of(name))
+    assert not np.array_equal(hostlib.generator(str(tmp_path / "b"), ln.N, ln.K), ln.gen)
+    other = nb.Decoder(ln.code, ln.prof["method"], ln.prof["max_iter"], poll_every=2, **decoder_kwargs(ln.prof))
+    other.set_demodulator(ln.order, ln.L, ln.src, ln.points)
+    with pytest.raises(nb.NblError) as e:
+        other.set_transmitter(gen=ln.gen, crc_len=ln.prof["crc_len"], random_msg=1, parallel=2, punct=ln.punct, mod_order=ln.order, n_mod_sym=ln.L)
+    assert e.value.status == -1 and "H * gen != 0" in str(e.value), e.value
+    other.close()
+    ln.dec.close()
 
 
 def _refused(ln, status, **over):

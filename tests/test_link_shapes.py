@@ -45,6 +45,32 @@ def test_table_covers_what_the_shipped_codes_do_not():
     assert any(left < i["K"] for i in infos.values() for _, left in i["swaps"])
 
 
+@pytest.mark.parametrize("name", ls.FIELD_SHAPES)
+def test_field_shapes_send_what_the_default_table_would_not(tmp_path, name):
+    """The two shapes with another modulus: their fixture (the compiled reference run on tables of that modulus) differs from what
+    the host chain sends with the default tables on the same graph, so a chain that ignored the table files would fail
+    test_host_chain_bit_exact; and the generator matrix is H's null space under the shape's table, not under the default one."""
+    import nbldpc_amd.datafiles as df
+    g, meta = load_golden(f"link_shape_{name}")
+    poly = ls.poly_of(name)
+    q = ls.SHAPES[name]["q"]
+    assert poly == meta["poly"] and df.is_primitive(q, poly) and poly != df.PRIMITIVE_POLY[q]
+    _, spec, info = ls.shape(name)
+    prepare_spec_workdir(str(tmp_path / "d"), meta["profile"], spec, np.array(meta["points"]))
+    _, tx, _, _ = hostlib.frontend(str(tmp_path / "d"), meta["ebn0"], meta["frames"], spec["N"], info["K"], q, meta["profile"]["parallel"])
+    assert not np.array_equal(tx, g["tx_code"])
+    prepare_spec_workdir(str(tmp_path / "a"), meta["profile"], spec, np.array(meta["points"]), poly=poly)
+    gen = hostlib.generator(str(tmp_path / "a"), spec["N"], info["K"])
+    syn = {}
+    for tag, (mul, _) in (("own", ls.gf_np(q, poly)), ("default", ls.gf_np(q))):
+        s = np.zeros((spec["M"], info["K"]), dtype=np.int64)
+        for m, row in enumerate(spec["chk_rows"]):
+            for v, h in row:
+                s[m] ^= mul[h, gen[v - 1].astype(np.int64)]       # gen [N][K]: code[n] = sum_k gen[n][k] msg[k]
+        syn[tag] = s
+    assert not syn["own"].any() and syn["default"].any()
+
+
 def test_stride_cases_follow_the_period_of_the_host_register():
     T = ls.pn_period()
     s0 = hostlib.pn_initial(0)
@@ -54,7 +80,7 @@ def test_stride_cases_follow_the_period_of_the_host_register():
 
 def _host(tmp_path, meta):
     spec, p = meta["spec"], meta["profile"]
-    prepare_spec_workdir(str(tmp_path), p, spec, np.array(meta["points"]))
+    prepare_spec_workdir(str(tmp_path), p, spec, np.array(meta["points"]), poly=meta.get("poly"))
     return hostlib.frontend(str(tmp_path), meta["ebn0"], meta["frames"], spec["N"], spec["N"] - spec["M"], spec["q"], p["parallel"])
 
 
@@ -62,7 +88,7 @@ def _host(tmp_path, meta):
 def test_host_chain_bit_exact(tmp_path, name):
     g, meta = load_golden(f"link_shape_{name}")
     assert meta["spec"] == json.loads(json.dumps(ls.shape(name)[1])) and meta["profile"] == ls.profile_of(name, meta["profile"]["parallel"])
-    assert np.array_equal(np.array(meta["points"]), ls.points_of(name))
+    assert np.array_equal(np.array(meta["points"]), ls.points_of(name)) and meta.get("poly") == ls.poly_of(name)
     L, tx, msg, sigma = _host(tmp_path, meta)
     assert sigma == g["sigma"][0]
     assert np.array_equal(tx, g["tx_code"])

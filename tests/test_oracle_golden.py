@@ -135,16 +135,48 @@ DEG_SETS = ["deg_all_gf16_ems", "deg_all_gf16_tems", "deg_all_gf16_bp", "deg_dc7
 DEG_BS_SETS = ["deg_all_gf16_bstems"]
 
 
+# ---- fields of another modulus: fixtures of tests/golden/make_golden_fields.py (the reference run on table files written with an
+# alternative primitive polynomial); the oracle LOADS the same table file instead of building its default table
+FIELD_SETS = ["field_gf16_m25_ems", "field_gf64_m91_tems", "field_gf256_m501_bp"]
+FIELD_RING = ("field_gf64_m91_tems", "field_gf256_m501_bp")    # graph A of tests/field_util.py, inside the shipped codes' box on purpose
+FIELD_BS_SETS = ["field_gf16_m25_bstems"]
+
+
+def _field_of(meta):
+    import field_util as fu
+    return fu.field(meta["spec"]["q"], meta["poly"]) if "poly" in meta else None
+
+
 def _mk_deg(oracle, meta, max_iter, mode):
     from degree_util import spec_edges
     _, edges = spec_edges(meta["spec"])
-    return oracle.Decoder(oracle.Code(edges=edges), oracle.GF(edges[2]), meta["profile"]["method"], int(max_iter), mode,
+    gf = _field_of(meta)
+    return oracle.Decoder(oracle.Code(edges=edges), oracle.GF(edges[2]) if gf is None else gf.oracle_gf(oracle), meta["profile"]["method"], int(max_iter), mode,
                           **decoder_kwargs(meta["profile"]))
+
+
+def _outside_the_box(meta):
+    return min(meta["chk_degs"]) < 4 or max(meta["chk_degs"]) > 5 or max(meta["var_degs"]) > 2
 
 
 def _check_deg(oracle, name, mode, exact):
     g, meta = load_golden(name)
-    assert min(meta["chk_degs"]) < 4 or max(meta["chk_degs"]) > 5 or max(meta["var_degs"]) > 2  # outside the shipped codes' box
+    assert "poly" not in meta and _outside_the_box(meta)  # outside the shipped codes' box
+    _check_fixture(oracle, g, meta, name, mode, exact)
+
+
+def _check_field(oracle, name, mode, exact):
+    g, meta = load_golden(name)
+    q = meta["spec"]["q"]
+    assert meta["poly"] != df.PRIMITIVE_POLY[q] and df.is_primitive(q, meta["poly"])
+    if name in FIELD_RING:
+        assert (meta["chk_degs"], meta["var_degs"]) == ([4], [2])
+    else:
+        assert _outside_the_box(meta)
+    _check_fixture(oracle, g, meta, name, mode, exact)
+
+
+def _check_fixture(oracle, g, meta, name, mode, exact):
     L = g["L_ch"]
     bp = meta["profile"]["method"] == 1
     frames = range(L.shape[0])
@@ -172,6 +204,31 @@ def test_degree_fixtures_literal_bit_exact(oracle, name):
     _check_deg(oracle, name, oracle.LITERAL, exact=True)
 
 
+@pytest.mark.parametrize("name", FIELD_SETS)
+def test_field_fixtures_literal_bit_exact(oracle, name):
+    """The literal oracle, its field LOADED from a table file of the fixture's modulus, equals the compiled reference run on the same
+    file bit for bit: decisions and flags of all 8 frames at every recorded iteration count, message state of the recorded frames."""
+    _check_field(oracle, name, oracle.LITERAL, exact=True)
+
+
+@pytest.mark.parametrize("name", FIELD_SETS)
+def test_field_fixtures_canonical_matches_reference_decisions(oracle, name):
+    _check_field(oracle, name, oracle.CANONICAL, exact=False)
+
+
+@pytest.mark.parametrize("name", FIELD_SETS)
+def test_field_fixtures_are_not_reproduced_by_the_default_table(oracle, name):
+    """The reference did read the table files of the other modulus: the literal oracle with the DEFAULT table does not give the
+    recorded check-to-variable messages of the first iteration (with the fixture's table it does, bit for bit, above)."""
+    from degree_util import spec_edges
+    g, meta = load_golden(name)
+    _, edges = spec_edges(meta["spec"])
+    dec = oracle.Decoder(oracle.Code(edges=edges), oracle.GF(edges[2]), meta["profile"]["method"], int(g["state_iters"][0]), oracle.LITERAL,
+                         **decoder_kwargs(meta["profile"]))
+    dec.decode(g["L_ch"][int(g["state_lanes"][0])])
+    assert not np.array_equal(dec.state()[2], g["st_c2v"][0, 0]), name
+
+
 @pytest.mark.parametrize("name", DEG_SETS)
 def test_degree_fixtures_canonical_matches_reference_decisions(oracle, name):
     _check_deg(oracle, name, oracle.CANONICAL, exact=False)
@@ -196,12 +253,27 @@ def test_degree_fixtures_ems_dynamic_program_equals_enumeration(oracle, name):
 def test_degree_fixtures_bstems_checker(tmp_path, name):
     """BS-TEMS has its own restatement (tests/bstems_check.cpp): literal mode bit for bit, canonical mode decisions / flags equal and
     state within 1e-9, on the graph with every degree."""
+    assert "poly" not in load_golden(name)[1]
+    _check_bstems(tmp_path, name)
+
+
+@pytest.mark.parametrize("name", FIELD_BS_SETS)
+def test_field_fixtures_bstems_checker(tmp_path, name):
+    """.. and with the tables of the fixture's modulus handed to the checker."""
+    meta = load_golden(name)[1]
+    assert meta["poly"] != df.PRIMITIVE_POLY[meta["spec"]["q"]] and _outside_the_box(meta)
+    _check_bstems(tmp_path, name)
+
+
+def _check_bstems(tmp_path, name):
     from bstems_util import CANONICAL, LITERAL, bs_kwargs, build_checker, run_checker
     from degree_util import spec_edges
     exe = build_checker(tmp_path)
     g, meta = load_golden(name)
     code, _ = spec_edges(meta["spec"])
     kw = bs_kwargs(meta["profile"])
+    if _field_of(meta) is not None:
+        kw["gf"] = _field_of(meta).tables
     L = g["L_ch"]
     lanes = [int(b) for b in g["state_lanes"]]
     for mode in (LITERAL, CANONICAL):

@@ -58,6 +58,32 @@ def test_null_gf_mat_is_refused():
     assert rc == -1 and b"gf_mat" in lib.nbl_last_error(None)
 
 
+def test_gf_mat_whose_element_1_is_not_the_identity_is_refused():
+    """Multiplying by 1 changes nothing: whatever basis gf_mat is written in, the matrix of element 1 is the identity.  One cleared
+    diagonal entry, one stray entry, and the set shifted by one element (a table indexed by the exponent instead of the element)."""
+    code = nb.Code(U128)
+    good = nb.datafiles.gf_matrices(16)
+    for method in (nb.METHOD_EMS, nb.METHOD_OSD):
+        m = good.copy()
+        m[1, 2, 2] = 0
+        _refused(code, -1, "element 1 is not the identity (entry [2][2])", method=method, osd_order=1, gf_mat=m)
+        m = good.copy()
+        m[1, 0, 3] = 1
+        _refused(code, -1, "element 1 is not the identity (entry [0][3])", method=method, osd_order=1, gf_mat=m)
+        _refused(code, -1, "element 1 is not the identity", method=method, osd_order=1, gf_mat=np.roll(good, 1, axis=0))
+    # and the matrices of another primitive modulus pass this check with their own tables
+    import torch
+    alt = nb.datafiles.gf_matrices(16, poly=25)
+    assert np.array_equal(alt[1], np.eye(4, dtype=np.uint8)) and not np.array_equal(alt, good)
+    gf = tuple(np.array(t, dtype=np.int64) for t in nb.datafiles.gf_tables(16, 25))
+    try:
+        _create(code, osd_order=1, gf=gf, gf_mat=alt).close()
+        assert torch.cuda.is_available()
+    except nb.NblError as e:
+        assert e.status in (-3, -2) and "identity" not in str(e) and (e.status == -2 or not torch.cuda.is_available()), str(e)
+        assert e.status == -3 or "full row rank" in str(e), str(e)
+
+
 def test_rank_deficient_matrix_is_refused():
     """Two identical check rows: [CRC rows; H_bit] loses full row rank; the reference's elimination would never end."""
     q = 16
