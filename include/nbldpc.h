@@ -160,15 +160,51 @@ nbl_status nbl_decode_batch_device(nbl_decoder *dec, const double *d_L_ch, int32
  * Replaces CComm::Demodulate (Comm.cpp:340-407) for the two cases the reference implements: BPSK (modOrder == 2, :342-380)
  * and one constellation point per code symbol (modOrder == GFq, :382-398), with the reference's expression order, so
  * the LLRs are bit-identical to the host computation.  Host->device traffic drops from N(q-1) doubles to 2 L doubles per
- * codeword (16x for BPSK GF(256), 128x for 256-QAM). */
+ * codeword (16x for BPSK GF(256), 128x for 256-QAM).
+ * Every other power-of-two order up to 256 (the branch the reference leaves open, Comm.cpp:400-404) runs through the GENERAL
+ * demodulator defined below (nbl_set_demodulator_ex). */
 typedef struct nbl_demod_desc {
-	int32_t mod_order;           /* 2, or q                                                              */
+	int32_t mod_order;           /* M = 2^m, 2 <= M <= 256                                               */
 	int32_t n_mod_sym;           /* L = received samples per codeword (MOD_SYM_LEN)                      */
-	const double *constellation; /* [mod_order][2] (Real, Image) = CONSTELLATION[]; used when mod_order == q */
+	const double *constellation; /* [mod_order][2] (Real, Image) = CONSTELLATION[]; required unless mod_order == 2 on the BPSK path */
 	const int32_t *src;          /* mod_order == 2: [N*p] sample index carrying code bit b, -1 = punctured (LLR 0, :350-354)
-	                                mod_order == q: [N]   sample index of code symbol n,    -1 = punctured (:386-393)   */
+	                                mod_order == q: [N]   sample index of code symbol n,    -1 = punctured (:386-393)
+	                                general path:   [N*p] label-bit index t carrying code bit b, -1 = not transmitted          */
 } nbl_demod_desc;
-nbl_status nbl_set_demodulator(nbl_decoder *dec, const nbl_demod_desc *demod);
+nbl_status nbl_set_demodulator(nbl_decoder *dec, const nbl_demod_desc *demod); /* = nbl_set_demodulator_ex(dec, demod, NULL) */
+
+/* ---- the general demodulator: any M = 2^m, 1 <= m <= 8, against any q = 2^p ------------------------------------------------
+ * Nothing in the reference computes these LLRs; the operation is defined here, operation by operation, so that independent
+ * implementations agree (tests/demod_general.py restates it in numpy).
+ *   Point s of a codeword (s < L) carries label bits (s, i), i = 0 .. m-1; label bit (s, i) has weight 2^(m-1-i) in the
+ *   constellation index (CComm::Modulate, Comm.cpp:319).  Linear label-bit index t = s m + i, t < L m.
+ *   src [N p]: src[n p + j] = the t that carries bit j (value 2^j) of code symbol n, or -1 when that bit is not transmitted.  Each t
+ *   may appear at most once and must be below L m (NBL_ERR_ARG otherwise, checked at the set call before anything is indexed).
+ *   Label bits nobody claims are legal and are marginalised; any src (a bit interleaver) is legal, a symbol may touch up to p points.
+ *   For symbol n: P(n) = its touched points, ascending s.  For s in P(n) the label positions of s claimed by n are "own", all
+ *   others "foreign".
+ *   Distance of table point c from the sample (re, im) of point s:   d_s(c) = (re - cr) * (re - cr) + (im - ci) * (im - ci)
+ *   C_s(a) = the indices c whose own positions equal the matching bits of value a.
+ *   NBL_DEMOD_MAXLOG:  D_s(a) = min of d_s(c) over C_s(a)
+ *   NBL_DEMOD_LOGSUM:  dmin = that minimum;
+ *                      D_s(a) = dmin - (2 sigma sigma) * log( sum over c in C_s(a), ascending c, of exp( -(d_s(c) - dmin) / (2 sigma sigma) ) )
+ *                      (the exact symbol likelihood under uniform foreign bits).  A point without a foreign position has one c
+ *                      per a: both metrics are d_s(c) and no exp / log is evaluated.
+ *   L[n][a-1] = sum over s in P(n), ascending, accumulated from 0.0, of (D_s(0) - D_s(a)) / (2 sigma sigma);  a = 0 has L = 0;
+ *   a symbol without a transmitted bit has all zeros; bits of a that are not transmitted change no C_s.
+ * mod_order == 2 and mod_order == q with force_general == 0 take exactly the two paths above (src [N] for mod_order == q);
+ * every other order takes the general path, as do these two with force_general == 1 (src [N p] then, constellation required): that
+ * flag exists so that the general kernel can be checked against the two reference-pinned ones.
+ * NBL_ERR_ARG with a message, before the device is touched: mod_order no power of two, below 2 or above 256; an unknown metric;
+ * a general path without constellation.  A refused call leaves the demodulator that was set before usable.
+ * Max-log LLRs are bit-identical between this library and the host layer; log-sum LLRs agree to rounding only (device exp / log). */
+#define NBL_DEMOD_LOGSUM 0
+#define NBL_DEMOD_MAXLOG 1
+typedef struct nbl_demod_ext {
+	int32_t metric;              /* NBL_DEMOD_*; read by the general path only */
+	int32_t force_general;
+} nbl_demod_ext;
+nbl_status nbl_set_demodulator_ex(nbl_decoder *dec, const nbl_demod_desc *demod, const nbl_demod_ext *ext /* may be NULL: log-sum, not forced */);
 /* rx: HOST buffer [B][L][2] (Real, Image) = RX_MOD_SYM after the channel; sigma = sigma_n (Comm.cpp:176-177) */
 nbl_status nbl_decode_batch_samples(nbl_decoder *dec, const double *rx, double sigma, int32_t B, int32_t *out_sym,
                                     uint8_t *converged, int32_t *iters);

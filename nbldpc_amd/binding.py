@@ -14,10 +14,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBL_HIP_LIB") or os.path.join(_HERE, "csrc", "libnbldpc_hip.so")  # NBL_HIP_LIB: A/B builds
 
 METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
+DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 
 # every symbol include/nbldpc.h declares
 EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
-           "nbl_set_demodulator", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
+           "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
            "nbl_workspace_bytes")
@@ -180,15 +181,26 @@ class Decoder:
         """Raw device pointers (ints); asynchronous on `stream` (a hipStream_t as int, None = decoder stream)."""
         self._chk(self.lib.nbl_decode_batch_device(self.h, d_L_ch, B, d_out, d_conv, d_iters, stream))
 
-    def set_demodulator(self, mod_order, n_mod_sym, src, constellation=None):
-        """src: int32 sample index per code bit (BPSK) / per code symbol (q-ary), -1 = punctured."""
+    def set_demodulator(self, mod_order, n_mod_sym, src, constellation=None, metric=None, force_general=False):
+        """src: int32 sample index per code bit (BPSK) / per code symbol (q-ary), -1 = punctured.  Any other order (and every order
+        with force_general): the general demodulator, src = label-bit index per code bit [N p], -1 = not transmitted, metric
+        DEMOD_LOGSUM (also None) or DEMOD_MAXLOG.  metric=None without force_general goes through nbl_set_demodulator."""
         class Demod(C.Structure):
             _fields_ = [("mod_order", C.c_int32), ("n_mod_sym", C.c_int32), ("constellation", C.c_void_p), ("src", C.c_void_p)]
-        self._dm_src = np.ascontiguousarray(src, dtype=np.int32)
-        self._dm_cons = None if constellation is None else np.ascontiguousarray(constellation, dtype=np.float64)
-        d = Demod(mod_order, n_mod_sym, None if self._dm_cons is None else self._dm_cons.ctypes.data, self._dm_src.ctypes.data)
-        self.lib.nbl_set_demodulator.argtypes = [C.c_void_p, C.c_void_p]
-        self._chk(self.lib.nbl_set_demodulator(self.h, C.byref(d)))
+
+        class DemodExt(C.Structure):
+            _fields_ = [("metric", C.c_int32), ("force_general", C.c_int32)]
+        dm_src = np.ascontiguousarray(src, dtype=np.int32)
+        dm_cons = None if constellation is None else np.ascontiguousarray(constellation, dtype=np.float64)
+        d = Demod(mod_order, n_mod_sym, None if dm_cons is None else dm_cons.ctypes.data, dm_src.ctypes.data)
+        if metric is None and not force_general:
+            self.lib.nbl_set_demodulator.argtypes = [C.c_void_p, C.c_void_p]
+            self._chk(self.lib.nbl_set_demodulator(self.h, C.byref(d)))
+        else:
+            ext = DemodExt(DEMOD_LOGSUM if metric is None else int(metric), int(bool(force_general)))
+            self.lib.nbl_set_demodulator_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            self._chk(self.lib.nbl_set_demodulator_ex(self.h, C.byref(d), C.byref(ext)))
+        self._dm_src, self._dm_cons = dm_src, dm_cons
 
     def decode_samples(self, rx, sigma):
         """rx: [B][L][2] received samples -> (out, converged, iters); L_ch is built on the device."""

@@ -50,6 +50,9 @@ struct nbl_decoder {
 	int dm_order = 0, dm_L = 0;
 	double *d_cons = nullptr;
 	int *d_src = nullptr;
+	bool dm_general = false;           // the general kernel (nbl_demod.hip): d_dmdesc in place of d_src
+	int dm_metric = 0;                 // NBL_DEMOD_*
+	NblDemodPoint *d_dmdesc = nullptr; // [N][p + 1]
 	double *d_rx = nullptr;
 	size_t d_rx_cap = 0;
 	// device-side AWGN channel (nbl_decode_batch_noise)
@@ -644,6 +647,7 @@ extern "C" void nbl_destroy(nbl_decoder *d)
 	for (void *p : d->graph_allocs) (void)hipFree(p);
 	if (d->d_src) (void)hipFree(d->d_src);
 	if (d->d_cons) (void)hipFree(d->d_cons);
+	if (d->d_dmdesc) (void)hipFree(d->d_dmdesc);
 	if (d->d_rx) (void)hipFree(d->d_rx);
 	for (double *p : d->d_rxs)
 		if (p) (void)hipFree(p);
@@ -986,43 +990,121 @@ extern "C" nbl_status nbl_decode_batch(nbl_decoder *d, const double *L_ch, int32
 	return NBL_OK;
 }
 
-extern "C" nbl_status nbl_set_demodulator(nbl_decoder *d, const nbl_demod_desc *dm)
+// The per-symbol descriptor of the general demodulator (nbl_common.h, NblDemodPoint) from src [N p]; every index is checked here,
+// before anything is indexed by it.
+static nbl_status build_demod_desc(nbl_decoder *d, const nbl_demod_desc *dm, int m, std::vector<NblDemodPoint> &desc)
+{
+	const int N = d->g.N, p = d->g.p;
+	const long long T = (long long)dm->n_mod_sym * m;
+	std::vector<uint8_t> seen((size_t)T, 0);
+	for (size_t i = 0; i < (size_t)N * p; i++) {
+		const int t = dm->src[i];
+		if (t < 0) continue;
+		if (t >= T) { d->err = "demodulator source index out of range (label bit " + std::to_string(t) + " of code bit " + std::to_string(i) + ", L * m = " + std::to_string(T) + ")"; return NBL_ERR_ARG; }
+		if (seen[t]) { d->err = "demodulator source: label bit " + std::to_string(t) + " is claimed twice"; return NBL_ERR_ARG; }
+		seen[t] = 1;
+	}
+	NblDemodPoint none{};
+	none.s = 0; none.nown = 0;
+	for (int i = 0; i < 8; i++) none.own[i] = -1;
+	desc.assign((size_t)N * (p + 1), none);
+	for (int n = 0; n < N; n++) {
+		NblDemodPoint *e = &desc[(size_t)n * (p + 1)];
+		int pts[8], nt = 0;
+		for (int j = 0; j < p; j++) {
+			const int t = dm->src[(size_t)n * p + j];
+			if (t < 0) continue;
+			const int s = t / m;
+			int k = 0;
+			while (k < nt && pts[k] != s) k++;
+			if (k == nt) pts[nt++] = s;
+		}
+		for (int x = 1; x < nt; x++) // ascending s
+			for (int y = x; y > 0 && pts[y - 1] > pts[y]; y--) { const int tmp = pts[y]; pts[y] = pts[y - 1]; pts[y - 1] = tmp; }
+		e[0].s = nt;
+		for (int k = 0; k < nt; k++) e[1 + k].s = pts[k];
+		for (int j = 0; j < p; j++) {
+			const int t = dm->src[(size_t)n * p + j];
+			if (t < 0) continue;
+			int k = 0;
+			while (pts[k] != t / m) k++;
+			e[1 + k].own[t % m] = (int8_t)j;
+			e[1 + k].nown++;
+		}
+	}
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_set_demodulator_ex(nbl_decoder *d, const nbl_demod_desc *dm, const nbl_demod_ext *ext)
 {
 	if (!d || !dm || !dm->src) return NBL_ERR_ARG;
 	const int q = d->g.q, N = d->g.N, p = d->g.p;
-	if (dm->mod_order != 2 && dm->mod_order != q) {
-		d->err = "This module ( code order ~= modulation order ) haven't been developed!"; // Comm.cpp:400-404
-		return NBL_ERR_UNSUPPORTED;
+	const int M = dm->mod_order;
+	// every refusal comes before the device and the handle's state are touched: the demodulator set before stays usable
+	if (M < 2 || M > 256 || (M & (M - 1))) {
+		d->err = "nbl_set_demodulator: mod_order " + std::to_string(M) + " is not a power of two in 2 .. 256";
+		return NBL_ERR_ARG;
 	}
-	if (dm->n_mod_sym <= 0 || (dm->mod_order == q && !dm->constellation)) return NBL_ERR_ARG;
+	const int metric = ext ? ext->metric : NBL_DEMOD_LOGSUM;
+	if (metric != NBL_DEMOD_LOGSUM && metric != NBL_DEMOD_MAXLOG) {
+		d->err = "nbl_set_demodulator_ex: unknown metric " + std::to_string(metric) + " (NBL_DEMOD_LOGSUM = 0, NBL_DEMOD_MAXLOG = 1)";
+		return NBL_ERR_ARG;
+	}
+	const bool general = (M != 2 && M != q) || (ext && ext->force_general);
+	if (dm->n_mod_sym <= 0) { d->err = "nbl_set_demodulator: n_mod_sym must be positive"; return NBL_ERR_ARG; }
+	if ((general || M == q) && !dm->constellation) {
+		d->err = "nbl_set_demodulator: this modulation order needs the constellation points (nbl_demod_desc.constellation)";
+		return NBL_ERR_ARG;
+	}
+	const int m = ilog2(M);
+	const size_t nsrc = (general || M == 2) ? (size_t)N * p : (size_t)N;
+	std::vector<NblDemodPoint> desc;
+	if (general) {
+		const nbl_status s = build_demod_desc(d, dm, m, desc);
+		if (s) return s;
+	} else {
+		for (size_t i = 0; i < nsrc; i++)
+			if (dm->src[i] >= dm->n_mod_sym) { d->err = "demodulator source index out of range"; return NBL_ERR_ARG; }
+	}
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
 	free_transmitter(d); // its geometry repeats the demodulator's: set it again afterwards
-	const size_t nsrc = dm->mod_order == 2 ? (size_t)N * p : (size_t)N;
-	for (size_t i = 0; i < nsrc; i++)
-		if (dm->src[i] >= dm->n_mod_sym) { d->err = "demodulator source index out of range"; return NBL_ERR_ARG; }
+	d->dm_order = 0;     // nothing is set until everything below has succeeded
 	if (d->d_src) (void)hipFree(d->d_src);
 	if (d->d_cons) (void)hipFree(d->d_cons);
-	d->d_src = nullptr; d->d_cons = nullptr;
-	HIP_TRY(d, hipMalloc((void **)&d->d_src, nsrc * 4));
-	HIP_TRY(d, hipMemcpy(d->d_src, dm->src, nsrc * 4, hipMemcpyHostToDevice));
-	if (dm->mod_order == q) {
-		HIP_TRY(d, hipMalloc((void **)&d->d_cons, (size_t)q * 16));
-		HIP_TRY(d, hipMemcpy(d->d_cons, dm->constellation, (size_t)q * 16, hipMemcpyHostToDevice));
+	if (d->d_dmdesc) (void)hipFree(d->d_dmdesc);
+	d->d_src = nullptr; d->d_cons = nullptr; d->d_dmdesc = nullptr;
+	if (general) {
+		HIP_TRY(d, hipMalloc((void **)&d->d_dmdesc, desc.size() * sizeof(NblDemodPoint)));
+		HIP_TRY(d, hipMemcpy(d->d_dmdesc, desc.data(), desc.size() * sizeof(NblDemodPoint), hipMemcpyHostToDevice));
+	} else {
+		HIP_TRY(d, hipMalloc((void **)&d->d_src, nsrc * 4));
+		HIP_TRY(d, hipMemcpy(d->d_src, dm->src, nsrc * 4, hipMemcpyHostToDevice));
 	}
 	d->h_cons.clear();
-	if (dm->constellation) d->h_cons.assign(dm->constellation, dm->constellation + (size_t)2 * dm->mod_order);
-	if (!d->d_cons && dm->constellation) { // BPSK: the demodulator does not need the points, the channel does
-		HIP_TRY(d, hipMalloc((void **)&d->d_cons, (size_t)dm->mod_order * 16));
-		HIP_TRY(d, hipMemcpy(d->d_cons, dm->constellation, (size_t)dm->mod_order * 16, hipMemcpyHostToDevice));
+	if (dm->constellation) { // (BPSK: the demodulator does not need the points, the channel does)
+		d->h_cons.assign(dm->constellation, dm->constellation + (size_t)2 * M);
+		HIP_TRY(d, hipMalloc((void **)&d->d_cons, (size_t)M * 16));
+		HIP_TRY(d, hipMemcpy(d->d_cons, dm->constellation, (size_t)M * 16, hipMemcpyHostToDevice));
 	}
 	// the channel's buffers are sized per lane of dm_L symbols and the jump table is per symbol position: both are rebuilt for
 	// the new L by the next channel call
 	if (d->d_jump) { (void)hipFree(d->d_jump); d->d_jump = nullptr; }
 	d->noise_cap = 0;
-	d->dm_order = dm->mod_order;
+	d->dm_general = general;
+	d->dm_metric = metric;
+	d->dm_order = M;
 	d->dm_L = dm->n_mod_sym;
 	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_set_demodulator(nbl_decoder *d, const nbl_demod_desc *dm) { return nbl_set_demodulator_ex(d, dm, nullptr); }
+
+// received samples -> L_ch in the workspace: the BPSK / q-ary kernel, or the general one where nbl_set_demodulator_ex chose it
+static hipError_t launch_demod(nbl_decoder *d, const double *d_rx, double sigma, int B)
+{
+	if (d->dm_general) return nbl_launch_demod_general(d_rx, d->dm_L, sigma, d->dm_order, d->dm_metric, d->d_cons, d->d_dmdesc, d->g, d->w, B, d->stream);
+	return nbl_launch_demod(d_rx, d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream);
 }
 
 static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_t st);
@@ -1045,7 +1127,7 @@ extern "C" nbl_status nbl_decode_batch_samples(nbl_decoder *d, const double *rx,
 		d->d_rx_cap = bytes;
 	}
 	HIP_TRY(d, hipMemcpyAsync(d->d_rx, rx, bytes, hipMemcpyHostToDevice, d->stream));
-	HIP_TRY(d, nbl_launch_demod(d->d_rx, d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream));
+	HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B));
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
 	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->w.done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
@@ -1205,7 +1287,7 @@ extern "C" nbl_status nbl_decode_batch_noise(nbl_decoder *d, const uint8_t *tx_i
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
 	if ((s = run_channel(d, tx_index, lane_state, sigma, B, d->stream, &d->d_rx, &d->d_rx_cap, d->err))) return s;
-	HIP_TRY(d, nbl_launch_demod(d->d_rx, d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream));
+	HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B));
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
 	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->w.done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
@@ -1248,7 +1330,7 @@ extern "C" nbl_status nbl_decode_batch_resident(nbl_decoder *d, int32_t slot, do
 	HIP_TRY(d, hipSetDevice(d->device));
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
-	HIP_TRY(d, nbl_launch_demod(d->d_rxs[slot], d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream));
+	HIP_TRY(d, launch_demod(d, d->d_rxs[slot], sigma, B));
 	if (d->tx.on) d->tx.dec_B[slot] = 0;
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	if (out_sym) HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));

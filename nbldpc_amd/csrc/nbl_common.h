@@ -36,6 +36,15 @@ struct NblGraphDev {
 	                    // when edge j IS the variable's first edge (one scalar load instead of a chain of four dependent ones)
 };
 
+// general demodulator (nbl_demod.hip): per code symbol p + 1 entries of 16 bytes.  Entry 0 is the header (s = number of touched
+// points); entries 1 .. are the touched points in ascending s: own[i] = the symbol bit j that label position i of the point carries,
+// -1 = a foreign position (another symbol's bit, or nobody's); nown = number of own positions.
+struct NblDemodPoint {
+	int32_t s;
+	int8_t own[8];
+	int32_t nown;
+};
+
 struct NblWork {
 	double *Lch, *v2c, *c2v, *post; // post only when state recording is on
 	const double *c2v_prev;         // fused EMS iteration: c2v of the previous iteration (read), c2v = this iteration (written)

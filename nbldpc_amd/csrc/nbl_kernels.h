@@ -6,6 +6,9 @@
 hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblWork &w, int B, int write_v2c, hipStream_t st);
 hipError_t nbl_launch_demod(const double *d_rx, int L, double sigma, int mod_order, const double *d_cons, const int *d_src,
                             const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
+// general demodulator, any mod_order = 2^m <= 256 (nbl_demod.hip); metric: NBL_DEMOD_* of include/nbldpc.h
+hipError_t nbl_launch_demod_general(const double *d_rx, int L, double sigma, int mod_order, int metric, const double *d_cons,
+                                    const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
 hipError_t nbl_launch_vn(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool damp, hipStream_t st);
 hipError_t nbl_launch_syn(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_compact(const uint8_t *done, int B, int *active, int *n_act, hipStream_t st);

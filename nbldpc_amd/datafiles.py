@@ -9,6 +9,7 @@ data files by tools/import_reference_data.py); the GF tables are GENERATED here 
 """
 import functools
 import json
+import math
 import os
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
@@ -36,6 +37,30 @@ def constellations():
     return _cons
 
 
+def gray_qam(order):
+    """Gray-labelled square QAM of `order` = 4^k points at unit average energy, by formula: the first k label bits (the high bits
+    of the index, CComm::Modulate is MSB first) choose the in-phase level, the last k the quadrature level; per axis the k bits are
+    a Gray code of the level number, level 0 = the most positive amplitude (index 0 -> (+, +), as BPSK's 0 -> +1).
+    [(index, re, im)] like constellations()'s entries."""
+    k = (order.bit_length() - 1) // 2
+    assert order == 4 ** k and k >= 1, order
+    n = 1 << k
+    amp = {g ^ (g >> 1): float(n - 1 - 2 * g) for g in range(n)}          # Gray code of level g -> amplitude n-1, n-3, .. -(n-1)
+    scale = math.sqrt(2.0 * (n * n - 1) / 3.0)                             # sqrt of the mean of re^2 + im^2 over the grid
+    return [(i, amp[i >> k] / scale, amp[i & (n - 1)] / scale) for i in range(order)]
+
+
+# constellations made by formula, beside the ones imported from the reference's data files
+GENERATED_CONSTELLATIONS = {"GRAY_QPSK": 4, "GRAY_16QAM": 16}
+
+
+def constellation(name):
+    """[(index, re, im)] of a shipped (constellations()) or generated (GENERATED_CONSTELLATIONS) constellation"""
+    if name in GENERATED_CONSTELLATIONS:
+        return gray_qam(GENERATED_CONSTELLATIONS[name])
+    return constellations()[name]
+
+
 def code_edges(name):
     """(N, M, q, edge_var, edge_chk, edge_h) with edges in var-major order, 0-based."""
     c = codes()[name]
@@ -61,7 +86,7 @@ def write_code_file(name, path):
 
 
 def write_constellation_file(name, path):
-    pts = constellations()[name]
+    pts = constellation(name)
     with open(path, "w") as f:
         f.write("\n".join(f"Point:\t{i}\tReal:\t{re!r}\tImag:\t{im!r}" for i, re, im in pts))
     return path

@@ -2,6 +2,8 @@
 // operation order, because L_ch has to be bit-identical for FER parity (tests/test_host_frontend.py).
 #include "comm.h"
 #include <cmath>
+#include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -55,10 +57,16 @@ bool CComm::Initial(CSimulation &sim, int lane, CNBLDPC *shared)
 	MOD_BIT_PER_SYM = log(sim.nQAM * 1.0) / log(2.0);
 	MOD_SYM_LEN = (CODE_SYM_LEN - PUN_SYM_LEN) * Bit_Len_PerSYM / MOD_BIT_PER_SYM;
 	MOD_BIT_LEN = MOD_SYM_LEN * MOD_BIT_PER_SYM;
-	if (modOrder != 2 && modOrder != GFq) {
-		error = "This module ( code order ~= modulation order ) haven't been developed!"; // Comm.cpp:400-404
+	// the reference stops at any order other than 2 and GFq (Comm.cpp:400-404); here those run through the general demodulator
+	if (modOrder < 2 || modOrder > 256 || (modOrder & (modOrder - 1)) || (1 << MOD_BIT_PER_SYM) != modOrder) {
+		error = "nQAM must be a power of two in 2 .. 256";
 		std::cerr << error << std::endl;
 		return false;
+	}
+	demod_metric = NBL_DEMOD_LOGSUM;
+	if (const char *e = getenv("NBL_DEMOD_METRIC")) {
+		if (!strcmp(e, "maxlog")) demod_metric = NBL_DEMOD_MAXLOG;
+		else if (strcmp(e, "logsum")) { error = "NBL_DEMOD_METRIC must be maxlog or logsum"; std::cerr << error << std::endl; return false; }
 	}
 
 	// constellation file: "Point: i Real: x Imag: y" per line (Comm.cpp:113-126)
@@ -152,10 +160,11 @@ void CComm::DemodSource(std::vector<int> &src) const
 {
 	src.clear();
 	int pi = 0;
-	if (modOrder == 2) {
+	if (modOrder == 2 || GeneralDemod()) {
+		const int limit = GeneralDemod() ? MOD_BIT_LEN : CODE_BIT_LEN; // BPSK: every kept bit has a sample
 		for (int b = 0; b < CODE_BIT_LEN; b++) {
 			if (PUN_BIT_LEN != 0 && pi < PUN_BIT_LEN && PUN_BIT[pi] == b) { pi++; src.push_back(-1); }
-			else src.push_back(b - pi);
+			else src.push_back(b - pi < limit ? b - pi : -1);
 		}
 	} else {
 		for (int s = 0; s < CODE_SYM_LEN; s++) {
@@ -312,7 +321,7 @@ int CComm::Puncture() // Comm.cpp:290-308
 	int pi = 0, mb = 0;
 	for (int b = 0; b < CODE_BIT_LEN; b++) {
 		if (PUN_BIT_LEN != 0 && pi < PUN_BIT_LEN && PUN_BIT[pi] == b) pi++;
-		else TX_MOD_BIT[mb++] = TX_CODE_BIT[b];
+		else if (mb < MOD_BIT_LEN) TX_MOD_BIT[mb++] = TX_CODE_BIT[b]; // (the tail MOD_SYM_LEN's floor drops: orders other than 2 and GFq only)
 	}
 	return 0;
 }
@@ -340,7 +349,14 @@ int CComm::Channel_AWGN() // Comm.cpp:328-337: real AND imaginary noise are draw
 int CComm::Demodulate() // Comm.cpp:340-407
 {
 	const int w = GFq - 1;
-	if (modOrder == 2) {
+	if (GeneralDemod()) {
+		std::vector<int> src;
+		DemodSource(src);
+		std::vector<double> cons, rx;
+		for (const CComplex &c : CONSTELLATION) { cons.push_back(c.Real); cons.push_back(c.Image); }
+		for (const CComplex &r : RX_MOD_SYM) { rx.push_back(r.Real); rx.push_back(r.Image); }
+		DemodulateGeneral(CODE_SYM_LEN, Bit_Len_PerSYM, modOrder, MOD_SYM_LEN, cons.data(), src.data(), rx.data(), sigma_n, demod_metric, RX_LLR_SYM.data());
+	} else if (modOrder == 2) {
 		int pi = 0;
 		for (int b = 0; b < CODE_BIT_LEN; b++) {
 			if (PUN_BIT_LEN != 0 && pi < PUN_BIT_LEN && PUN_BIT[pi] == b) { pi++; RX_LLR_BIT[b] = 0; }
@@ -372,6 +388,63 @@ int CComm::Demodulate() // Comm.cpp:340-407
 		}
 	}
 	return 0;
+}
+
+// include/nbldpc.h, "the general demodulator", statement by statement
+void CComm::DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric,
+                              double *out)
+{
+	(void)L;
+	const int q = 1 << p;
+	int m = 0;
+	while ((1 << m) < M) m++;
+	std::vector<double> d(M), D(q);
+	for (int n = 0; n < N; n++) {
+		double *Ln = out + (size_t)n * (q - 1);
+		for (int a = 1; a < q; a++) Ln[a - 1] = 0.0;
+		// P(n): touched points, ascending s
+		std::vector<int> pts;
+		for (int j = 0; j < p; j++) {
+			const int t = src[n * p + j];
+			if (t >= 0) pts.push_back(t / m);
+		}
+		std::sort(pts.begin(), pts.end());
+		pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+		for (int s : pts) {
+			// own positions of s: label position i carries bit owner[i] of symbol n (-1: foreign)
+			int owner[8], nown = 0;
+			for (int i = 0; i < m; i++) owner[i] = -1;
+			for (int j = 0; j < p; j++) {
+				const int t = src[n * p + j];
+				if (t >= 0 && t / m == s) { owner[t % m] = j; nown++; }
+			}
+			const double re = rx[2 * s], im = rx[2 * s + 1];
+			for (int c = 0; c < M; c++) {
+				const double cr = cons[2 * c], ci = cons[2 * c + 1];
+				d[c] = (re - cr) * (re - cr) + (im - ci) * (im - ci);
+			}
+			for (int a = 0; a < q; a++) {
+				// C_s(a): label bit (s, i) of c is bit m-1-i of c
+				auto compatible = [&](int c) {
+					for (int i = 0; i < m; i++)
+						if (owner[i] >= 0 && ((c >> (m - 1 - i)) & 1) != ((a >> owner[i]) & 1)) return false;
+					return true;
+				};
+				bool first = true;
+				double dmin = 0.0;
+				for (int c = 0; c < M; c++)
+					if (compatible(c) && (first || d[c] < dmin)) { dmin = d[c]; first = false; }
+				if (metric == NBL_DEMOD_MAXLOG || nown == m) D[a] = dmin;
+				else {
+					double sum = 0.0;
+					for (int c = 0; c < M; c++)
+						if (compatible(c)) sum = sum + exp(-(d[c] - dmin) / (2 * sigma * sigma));
+					D[a] = dmin - (2 * sigma * sigma) * log(sum);
+				}
+			}
+			for (int a = 1; a < q; a++) Ln[a - 1] = Ln[a - 1] + (D[0] - D[a]) / (2 * sigma * sigma);
+		}
+	}
 }
 
 int CComm::TakeDecoded(const int *decoded, bool converged) // Comm.cpp:421-443

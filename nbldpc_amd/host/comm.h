@@ -23,6 +23,7 @@ public:
 	int MSG_SYM_LEN = 0, MSG_BIT_LEN = 0, CODE_SYM_LEN = 0, CODE_BIT_LEN = 0, PUN_SYM_LEN = 0, PUN_BIT_LEN = 0;
 	int modOrder = 0, MOD_BIT_PER_SYM = 0, MOD_SYM_LEN = 0, MOD_BIT_LEN = 0;
 	double CodeRate = 0, sigma_n = 0;
+	int demod_metric = 0;              // NBL_DEMOD_* of the general demodulator (modOrder other than 2 and GFq): NBL_DEMOD_METRIC=maxlog|logsum
 	std::vector<int> TX_MSG_BIT_beforeCRC, TX_MSG_BIT, TX_MSG_SYM, TX_CODE_SYM, TX_CODE_BIT, PUN_SYM, PUN_BIT, TX_MOD_BIT;
 	std::vector<int> RX_DECODE_SYM, RX_DECODE_BIT, RX_MSG_SYM, RX_MSG_BIT;
 	std::vector<CComplex> CONSTELLATION, TX_MOD_SYM, RX_MOD_SYM;
@@ -38,7 +39,14 @@ public:
 	// everything up to Modulate: channel and demodulator run on the device.  The lane's generator state in front of the frame is
 	// returned and the generator is moved past the 4 * MOD_SYM_LEN uniform draws Channel_AWGN would have made (Comm.cpp:328-337).
 	int FrontEndToModulate(unsigned int state_out[3]);
-	void DemodSource(std::vector<int> &src) const; // which received sample carries each code bit (BPSK) / code symbol (q-ary)
+	// which received sample carries each code bit (BPSK) / code symbol (q-ary); any other order: which label bit t = s m + i carries
+	// each code bit (kept bit k goes to t = k, -1 once k >= MOD_SYM_LEN m: the tail that MOD_SYM_LEN's floor drops)
+	void DemodSource(std::vector<int> &src) const;
+	bool GeneralDemod() const { return modOrder != 2 && modOrder != GFq; }
+	// The general demodulator of include/nbldpc.h (nbl_set_demodulator_ex) restated literally, libm exp / log: N symbols of p bits, M
+	// = 2^m points cons [M][2], src [N p], samples rx [L][2] -> out [N][2^p - 1].  src is taken as checked (each t once, below L m).
+	static void DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric,
+	                              double *out);
 	int GenerateMessage();
 	int GenPN();
 	void CRCEncode(int *seqOut, const int *seqIn, int seqInLen, int crcLen, int crc24Type);

@@ -51,9 +51,9 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 		lanes[0]->DemodSource(src);
 		std::vector<double> cons;
 		for (const CComplex &c : lanes[0]->CONSTELLATION) { cons.push_back(c.Real); cons.push_back(c.Image); }
-		if (code.SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data()) != 0) { error = code.LastError(); return false; }
+		if (code.SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data(), lanes[0]->demod_metric) != 0) { error = code.LastError(); return false; }
 		for (auto &x : extra)
-			if (x->SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data()) != 0) { error = x->LastError(); return false; }
+			if (x->SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data(), lanes[0]->demod_metric) != 0) { error = x->LastError(); return false; }
 	}
 	if (device_tx) {
 		CComm &l0 = *lanes[0];

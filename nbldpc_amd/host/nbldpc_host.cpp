@@ -207,11 +207,12 @@ int CNBLDPC::DecodingBatch(const double *L_ch, int B, int *out, uint8_t *converg
 	return 0;
 }
 
-int CNBLDPC::SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src)
+int CNBLDPC::SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src, int metric)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }
 	nbl_demod_desc dm = {mod_order, n_mod_sym, constellation, src};
-	nbl_status st = nbl_set_demodulator(dec, &dm);
+	nbl_demod_ext ext = {metric, 0}; // orders 2 and GFq: the two reference-pinned paths, the metric is not read
+	nbl_status st = nbl_set_demodulator_ex(dec, &dm, &ext);
 	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
 	return 0;
 }

@@ -37,7 +37,7 @@ public:
 	// L_ch [B][CodeLen][GFq-1]; out [B][CodeLen]; converged [B] (may be null); iters [B] (may be null). 0 on success.
 	int DecodingBatch(const double *L_ch, int B, int *out, uint8_t *converged, int *iters);
 	// device-side demodulation (replaces CComm::Demodulate, Comm.cpp:340-407): rx [B][L][2] received samples
-	int SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src);
+	int SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src, int metric = 0); // metric: NBL_DEMOD_*, general orders only
 	int DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters);
 	// device-side channel (replaces CComm::Channel_AWGN + CRand, Comm.cpp:328-337 / Rand.cpp:17-37): tx_index [B][L] constellation
 	// indices, lane_state [B][3] generator states in front of the frame

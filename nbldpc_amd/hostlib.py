@@ -25,6 +25,7 @@ def load():
         L = C.CDLL(HOST_LIB)
         L.nblh_frontend.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.nblh_channel.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.nblh_demod_general.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
         L.nblh_simulate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int]
         L.nblh_encode.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
         L.nblh_generator.argtypes = [C.c_char_p, C.c_void_p]
@@ -86,6 +87,21 @@ def channel(workdir_path, ebn0, frames, L, P):
     if rc != L:
         raise RuntimeError(f"nblh_channel rc={rc} (expected MOD_SYM_LEN {L})")
     return rx, txi, state, sig.value
+
+
+def demod_general(N, p, points, src, rx, sigma, metric):
+    """CComm::DemodulateGeneral (the host layer's statement of nbl_set_demodulator_ex's general path) on rx [B][L][2] -> [B][N][2^p - 1].
+    points [M][2], src [N p] label-bit index per code bit (-1 = not transmitted), metric 0 = log-sum, 1 = max-log.  No GPU."""
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    src = np.ascontiguousarray(src, dtype=np.int32)
+    rx = np.ascontiguousarray(rx, dtype=np.float64)
+    B, L = rx.shape[0], rx.shape[1]
+    assert src.shape == (N * p,) and rx.shape == (B, L, 2) and points.shape[1] == 2
+    out = np.zeros((B, N, (1 << p) - 1))
+    rc = load().nblh_demod_general(N, p, points.shape[0], L, points.ctypes.data, src.ctypes.data, rx.ctypes.data, float(sigma), int(metric), B, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"nblh_demod_general rc={rc}")
+    return out
 
 
 def simulate(workdir_path, device=0, max_rows=32):
