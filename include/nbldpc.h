@@ -144,6 +144,43 @@ nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, con
                           const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out);
 void nbl_destroy(nbl_decoder *dec);
 
+/* ---- the layered (check-serial) schedule for EMS ------------------------------------------------------------------------------
+ * Every other entry point runs the reference's flooding schedule: in each iteration all variables update, then all checks
+ * (NBLDPC.cpp:805-918).  In a layered schedule a check reads the messages its neighbours wrote earlier in the SAME iteration, and a
+ * frame converges in fewer iterations.  Nothing in the reference computes it; the operation is defined here, operation by operation,
+ * so that independent implementations agree (tests/layered_ref.py restates it in numpy on top of the reference-pinned check-node
+ * update).
+ *   A layer assignment layer_of[M] maps every check to a layer 0 .. n_layers-1; every layer is non-empty and no two checks of one
+ *   layer share a variable.  The result depends on the assignment, so the assignment is an input.
+ *   State: c2v[E], all zero before iteration 1.  Iteration it = 1 .. max_iter:
+ *   1. Tentative decision and syndrome, exactly as flooding (NBLDPC.cpp:808-846): post[n] = L_ch[n], then += c2v of the variable's
+ *      edges in the variable's edge order; DecideLLRVector; the syndrome.  The first zero syndrome freezes out_sym, sets converged
+ *      and iters = it (and, with fixed_iters == 0, ends the frame: its c2v stay as iteration it-1 left them).  fixed_iters and
+ *      poll_every keep their meaning.
+ *   2. For l = 0 .. n_layers-1, for every check m with layer_of[m] == l:
+ *        for every edge k of m, with variable n:
+ *          P = L_ch[n];  P += c2v[e] for each edge e of n, in n's edge order, reading the CURRENT values;  v2c_k = P - c2v[(m,k)]
+ *          (the reference's AddLLRVector / MinusLLRVector expressions, :810-817 and :855; slot 0 of a vector is 0; no other
+ *          normalisation)
+ *        c2v[(m, .)] = the EMS check-node update of v2c_0 .. v2c_{dc-1} (:859-917): the canonical, residue-free value every EMS
+ *        kernel of this library computes.
+ *      The order inside a layer is immaterial: the checks of a layer share no variable.
+ *   With one layer per check, in check order, this is the serial-C schedule.
+ * nbl_layer_greedy: pure host arithmetic, no device: the library's default assignment.  Checks in ascending index, each gets the
+ * smallest layer that holds no check sharing a variable with it.  Returns n_layers, or a negative nbl_status.
+ * nbl_create_layered: nbl_create with this schedule; layer_of == NULL: nbl_layer_greedy's.  NBL_METHOD_EMS only (no OSD, no
+ * extension parameters).  Refused at creation, before the device is touched, with a message: NBL_ERR_ARG for a layer index below 0,
+ * an empty layer below the largest index used, two checks of one layer sharing a variable (the message names both checks and the
+ * variable); NBL_ERR_UNSUPPORTED for any other method (methods 1, 4 and 7 damp against the previous iteration's decision in their
+ * variable-node pass, which has no layered counterpart); and everything nbl_create refuses, the same way.
+ * Every decode call, the demodulator, channel, transmitter and error count work unchanged on such a decoder.  nbl_read_state returns
+ * post (with nbl_set_record_state) and c2v as defined above; v2c is never materialised: a non-NULL v2c is NBL_ERR_UNSUPPORTED.
+ * nbl_get_layers: the assignment in use (host arrays; either may be NULL); NBL_ERR_ARG on a flooding decoder. */
+int32_t nbl_layer_greedy(const nbl_code_desc *code, int32_t *layer_of /* [M] */);
+nbl_status nbl_create_layered(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
+                              const nbl_params *params, const int32_t *layer_of, int device, nbl_decoder **out);
+nbl_status nbl_get_layers(const nbl_decoder *dec, int32_t *layer_of, int32_t *n_layers);
+
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the
  * reference's return value).  iters: [B] iteration of the first zero syndrome, or max_iter.

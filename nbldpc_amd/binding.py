@@ -17,7 +17,7 @@ METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
@@ -79,6 +79,12 @@ def load_library():
         L.nbl_create_osd.restype = C.c_int
         L.nbl_create_osd.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(ParamsExt),
                                      C.POINTER(OsdParams), C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_layer_greedy.restype = C.c_int32
+        L.nbl_layer_greedy.argtypes = [C.POINTER(CodeDesc), C.c_void_p]
+        L.nbl_create_layered.restype = C.c_int
+        L.nbl_create_layered.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_get_layers.restype = C.c_int
+        L.nbl_get_layers.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.nbl_destroy.argtypes = [C.c_void_p]
         L.nbl_destroy.restype = None
         L.nbl_decode_batch.restype = C.c_int
@@ -118,17 +124,31 @@ class Code:
                         self.var_chk.ctypes.data, self.var_h.ctypes.data, self.chk_var.ctypes.data, self.chk_h.ctypes.data)
 
 
+def layer_greedy(code):
+    """The library's default layer assignment of the layered schedule (nbl_layer_greedy; host arithmetic, no device):
+    layer_of [M] int32.  Checks in ascending index, each in the smallest layer that holds no check sharing a variable with it."""
+    lib = load_library()
+    layer_of = np.zeros(code.M, dtype=np.int32)
+    desc = code.desc()
+    rc = lib.nbl_layer_greedy(C.byref(desc), layer_of.ctypes.data)
+    if rc < 0:
+        raise NblError(rc, lib.nbl_last_error(None).decode())
+    assert rc == int(layer_of.max()) + 1
+    return layer_of
+
+
 class Decoder:
     """Batched decoder handle (nbl_create .. nbl_destroy).  Basic-set T-EMS (method 7) takes bs_nm / bs_nc / bs_factor / bs_offset
     through nbl_create_ex; without bs_nm the handle is made by nbl_create, which refuses method 7.  OSD (method 6, or post-processing
     of methods 1/2/4/7 with osd_order >= 0) takes osd_* / crc_len / crc_rows / gf_mat through nbl_create_osd; with osd_order=None the
     handle is made as before, so method 6 is refused.  gf_mat=None: the GF element matrices as the reference's loader leaves them
-    (datafiles.gf_matrices(q, as_loaded=True))."""
+    (datafiles.gf_matrices(q, as_loaded=True)).  layers: None = the flooding schedule; "greedy" or an int array [M] (a layer per
+    check) = the layered schedule through nbl_create_layered (EMS only; no bs_* / osd_* parameters go with it)."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None):
+                 gf_mat=None, layers=None):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -138,7 +158,15 @@ class Decoder:
                              tems_offset, fixed_iters, poll_every, max_batch)
         desc = code.desc()
         h = C.c_void_p()
-        if osd_order is not None:
+        if layers is not None:
+            if osd_order is not None or bs_nm is not None:
+                raise ValueError("layers: nbl_create_layered takes neither OSD nor extension parameters")
+            self._layer_of = None if isinstance(layers, str) and layers == "greedy" else np.ascontiguousarray(layers, dtype=np.int32)
+            if self._layer_of is not None and self._layer_of.shape != (code.M,):
+                raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
+            rc = self.lib.nbl_create_layered(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params),
+                                             None if self._layer_of is None else self._layer_of.ctypes.data, device, C.byref(h))
+        elif osd_order is not None:
             self._gf_mat = np.ascontiguousarray(datafiles.gf_matrices(code.q) if gf_mat is None else gf_mat, dtype=np.uint8)
             self.osd = OsdParams(osd_order, osd_flag, osd_factor, crc_len, crc_rows, self._gf_mat.ctypes.data)
             self.ext = ParamsExt(bs_nm, bs_nc, bs_factor, bs_offset) if bs_nm is not None else None
@@ -161,6 +189,16 @@ class Decoder:
 
     def __del__(self):
         self.close()
+
+    @property
+    def layers(self):
+        """The layer assignment in use, [M] int32 (nbl_get_layers); None on a flooding decoder."""
+        layer_of = np.zeros(self.code.M, dtype=np.int32)
+        n = C.c_int32(0)
+        if self.lib.nbl_get_layers(self.h, layer_of.ctypes.data, C.byref(n)) != 0:
+            return None
+        assert n.value == int(layer_of.max()) + 1
+        return layer_of
 
     def _chk(self, rc):
         if rc != 0:
@@ -336,12 +374,13 @@ class Decoder:
         self._chk(self.lib.nbl_last_timing(self.h, ms, ln))
         return list(ms), list(ln)
 
-    def read_state(self, b, post=True):
+    def read_state(self, b, post=True, v2c=True):
+        """(post, v2c, c2v) of codeword b; post=False / v2c=False pass NULL and return None in that place (a layered decoder has no v2c)"""
         w, N, E = self.code.q - 1, self.code.N, self.code.E
         P = np.zeros((N, w)) if post else None
-        V = np.zeros((E, w))
+        V = np.zeros((E, w)) if v2c else None
         Cc = np.zeros((E, w))
-        self._chk(self.lib.nbl_read_state(self.h, b, P.ctypes.data if post else None, V.ctypes.data, Cc.ctypes.data))
+        self._chk(self.lib.nbl_read_state(self.h, b, P.ctypes.data if post else None, V.ctypes.data if v2c else None, Cc.ctypes.data))
         return P, V, Cc
 
     def workspace_bytes(self):

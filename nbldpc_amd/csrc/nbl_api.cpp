@@ -46,6 +46,12 @@ struct nbl_decoder {
 	                            // have to be cleared on every call)
 	const double *last_c2v = nullptr;
 	bool last_fused = false;    // the last decode ran fused iterations (nbl_read_state picks the c2v buffer per codeword)
+	// layered (check-serial) schedule (nbl_create_layered): EMS only, one c2v buffer updated in place, no v2c
+	bool layered = false;
+	int n_layers = 0;
+	std::vector<int> h_layer_of; // [M] the assignment in use
+	std::vector<int> h_lay_off;  // [n_layers + 1] offsets into ly.chk
+	NblLayerDev ly{};
 	// device-side demodulator (nbl_set_demodulator)
 	int dm_order = 0, dm_L = 0;
 	double *d_cons = nullptr;
@@ -205,6 +211,7 @@ static bool ems64_shape(const nbl_decoder *d)
 
 static bool fused_shape(const nbl_decoder *d)
 {
+	if (d->layered) return false; // (the fused kernels ARE the flooding schedule: c2v double-buffered)
 	// (variable degrees above 3: these kernels behind the separate VN pass)
 	if (small_shape(d) || ems64_shape(d)) return d->g.c_nbr != nullptr;
 	if (!d->all_dv2) return false;
@@ -219,7 +226,7 @@ static nbl_status ensure_workspace(nbl_decoder *d, int B)
 {
 	// v2c only exists in HBM when something reads it: the unfused path, or state read-back
 	// (damped methods always keep it: the damping reads the previous iteration's v2c)
-	const bool want_v2c = d->prm.method != NBL_METHOD_EMS || !fused_shape(d) || d->record_state || d->force_generic != 0;
+	const bool want_v2c = !d->layered && (d->prm.method != NBL_METHOD_EMS || !fused_shape(d) || d->record_state || d->force_generic != 0);
 	const bool want_post = d->record_state || d->osd_acc;
 	if (B <= d->cap && (!want_post || d->w.post) && (!want_v2c || d->w.v2c)) return NBL_OK;
 	int cap = B > d->cap ? B : d->cap;
@@ -415,8 +422,104 @@ static int validate_field(int q, const uint16_t *gf_mul, const uint16_t *gf_inv,
 	return poly;
 }
 
+// ---- layer assignments of the layered schedule (include/nbldpc.h): pure host arithmetic --------------------------------------
+// Greedy colouring on a checked graph: checks in ascending index, each gets the smallest layer that holds no check sharing a
+// variable with it.  Returns the number of layers.
+static int layer_greedy(int N, int M, const std::vector<int> &coff, const int32_t *chk_var, int32_t *layer_of)
+{
+	std::vector<std::vector<int>> used(N);  // layers of the checks each variable has joined so far
+	std::vector<int> stamp(M + 1, -1);
+	int n_layers = 0;
+	for (int m = 0; m < M; m++) {
+		for (int ce = coff[m]; ce < coff[m + 1]; ce++)
+			for (int l : used[chk_var[ce]]) stamp[l] = m;
+		int l = 0;
+		while (stamp[l] == m) l++; // (at most M - 1 layers are taken: stamp[M] is never reached)
+		layer_of[m] = l;
+		if (l + 1 > n_layers) n_layers = l + 1;
+		for (int ce = coff[m]; ce < coff[m + 1]; ce++) {
+			std::vector<int> &u = used[chk_var[ce]];
+			bool have = false;
+			for (int x : u) have = have || x == l;
+			if (!have) u.push_back(l);
+		}
+	}
+	return n_layers;
+}
+
+// A caller's assignment: every index >= 0, every layer up to the largest index used non-empty, no two checks of a layer sharing a
+// variable.  Returns the number of layers, or 0 with the offence named in `msg`.
+static int layer_validate(int N, int M, const std::vector<int> &coff, const int32_t *chk_var, const int32_t *layer_of, std::string &msg)
+{
+	int n_layers = 0;
+	for (int m = 0; m < M; m++) {
+		if (layer_of[m] < 0) { msg = "layered schedule: layer_of[" + std::to_string(m) + "] = " + std::to_string(layer_of[m]) + " is below 0"; return 0; }
+		if (layer_of[m] >= M) { msg = "layered schedule: layer " + std::to_string(layer_of[m]) + " of check " + std::to_string(m) + " leaves an empty layer below it (M = " + std::to_string(M) + " checks)"; return 0; }
+		if (layer_of[m] + 1 > n_layers) n_layers = layer_of[m] + 1;
+	}
+	std::vector<int> count(n_layers, 0);
+	for (int m = 0; m < M; m++) count[layer_of[m]]++;
+	for (int l = 0; l < n_layers; l++)
+		if (!count[l]) { msg = "layered schedule: layer " + std::to_string(l) + " is empty (the largest layer index used is " + std::to_string(n_layers - 1) + ")"; return 0; }
+	// per variable: the check that claimed each layer first
+	std::vector<std::vector<std::pair<int, int>>> seen(N);
+	for (int m = 0; m < M; m++)
+		for (int ce = coff[m]; ce < coff[m + 1]; ce++) {
+			const int n = chk_var[ce];
+			for (const auto &pr : seen[n])
+				if (pr.first == layer_of[m] && pr.second != m) {
+					msg = "layered schedule: checks " + std::to_string(pr.second) + " and " + std::to_string(m) + " of layer " + std::to_string(layer_of[m]) + " share variable " + std::to_string(n);
+					return 0;
+				}
+			seen[n].push_back({layer_of[m], m});
+		}
+	return n_layers;
+}
+
+extern "C" int32_t nbl_layer_greedy(const nbl_code_desc *code, int32_t *layer_of)
+{
+	if (!code || !layer_of || !code->chk_deg || !code->chk_var) { g_create_error = "null argument"; return NBL_ERR_ARG; }
+	const int N = code->N, M = code->M;
+	if (N <= 0 || M <= 0) { g_create_error = "N, M must be positive"; return NBL_ERR_ARG; }
+	std::vector<int> coff(M + 1, 0);
+	for (int m = 0; m < M; m++) {
+		if (code->chk_deg[m] < 1 || code->chk_deg[m] > N) { g_create_error = "check degree out of range"; return NBL_ERR_ARG; }
+		coff[m + 1] = coff[m] + code->chk_deg[m];
+	}
+	for (int ce = 0; ce < coff[M]; ce++)
+		if (code->chk_var[ce] < 0 || code->chk_var[ce] >= N) { g_create_error = "check-side edge out of range"; return NBL_ERR_ARG; }
+	return layer_greedy(N, M, coff, code->chk_var, layer_of);
+}
+
+// nbl_create_layered's request: layer_of == NULL asks for the greedy assignment
+struct LayerReq { const int32_t *layer_of; };
+
+static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out);
+
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
+{
+	return create_impl(code, gf_mul, gf_inv, params, ext, osd, nullptr, device, out);
+}
+
+extern "C" nbl_status nbl_create_layered(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                         const int32_t *layer_of, int device, nbl_decoder **out)
+{
+	const LayerReq lay = {layer_of};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
+}
+
+extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
+{
+	if (!d || !d->layered) return NBL_ERR_ARG;
+	if (layer_of) memcpy(layer_of, d->h_layer_of.data(), d->h_layer_of.size() * sizeof(int32_t));
+	if (n_layers) *n_layers = d->n_layers;
+	return NBL_OK;
+}
+
+static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out)
 {
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
@@ -428,6 +531,9 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 	std::string field_err;
 	const int poly = validate_field(q, gf_mul, gf_inv, field_err);
 	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
+	if (lay && params->method != NBL_METHOD_EMS)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the layered schedule is defined for EMS (method 2) only: the other methods damp against the previous iteration's "
+		                                                 "decision in their variable-node pass and stay flooding-only");
 	switch (params->method) {
 	case NBL_METHOD_EMS: case NBL_METHOD_BP: case NBL_METHOD_TEMS: break;
 	case NBL_METHOD_BS_TEMS:
@@ -544,6 +650,38 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 		if (!special && lds > 160 * 1024)
 			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
 	}
+	// ---- layered schedule: the assignment, checked or made here, before the device is touched ----
+	std::vector<int> layer_of, lay_off, lay_chk, lay_nbr;
+	int n_layers = 0;
+	if (lay) {
+		// (the layered kernel is the general one: no specialised shape stands in for it, so the LDS bound holds for every shape)
+		const int dl = (params->ems_nc >= maxdc - 1) ? 1 : params->ems_nc + 1;
+		const size_t lds = ((size_t)maxdc * q + (2 * (size_t)dl + 1) * q + (size_t)maxdc * params->ems_nm) * 8 + (size_t)maxdc * params->ems_nm * 4 + 16;
+		if (lds > 160 * 1024)
+			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
+		layer_of.assign(M, 0);
+		if (lay->layer_of) {
+			std::string lerr;
+			n_layers = layer_validate(N, M, coff, code->chk_var, lay->layer_of, lerr);
+			if (!n_layers) return fail_create(nullptr, NBL_ERR_ARG, lerr);
+			layer_of.assign(lay->layer_of, lay->layer_of + M);
+		} else {
+			n_layers = layer_greedy(N, M, coff, code->chk_var, layer_of.data());
+		}
+		lay_off.assign(n_layers + 1, 0);
+		for (int m = 0; m < M; m++) lay_off[layer_of[m] + 1]++;
+		for (int l = 0; l < n_layers; l++) lay_off[l + 1] += lay_off[l];
+		lay_chk.assign(M, 0);
+		std::vector<int> fill(lay_off.begin(), lay_off.end() - 1);
+		for (int m = 0; m < M; m++) lay_chk[fill[layer_of[m]]++] = m;
+		lay_nbr.assign((size_t)E * NBL_LAYER_ROW, 0);
+		for (int ce = 0; ce < E; ce++) {
+			const int n = c_var[ce], e0 = voff[n], dv = voff[n + 1] - e0;
+			lay_nbr[(size_t)ce * NBL_LAYER_ROW] = n;
+			lay_nbr[(size_t)ce * NBL_LAYER_ROW + 1] = dv;
+			for (int k = 0; k < dv; k++) lay_nbr[(size_t)ce * NBL_LAYER_ROW + 4 + k] = v_cpos[e0 + k];
+		}
+	}
 
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail_create(nullptr, NBL_ERR_NO_DEVICE, "no HIP device (this library has no CPU decode path)");
@@ -574,6 +712,13 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 		d->osd.flag = params->method == NBL_METHOD_OSD ? 1 : osd->flag;
 		d->osd_factor = osd->factor;
 		d->osd_acc = d->osd.flag == 0;
+	}
+	if (lay) {
+		if ((st = upload(d, lay_chk, &d->ly.chk)) || (st = upload(d, lay_nbr, &d->ly.nbr))) return fail_create(d, st, "");
+		d->layered = true;
+		d->n_layers = n_layers;
+		d->h_layer_of = layer_of;
+		d->h_lay_off = lay_off;
 	}
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
@@ -786,6 +931,19 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 	const nbl_params &p = d->prm;
 	for (int it = it_lo; it <= it_hi; it++) {
 		c.r.iter = it;
+		if (d->layered) {
+			// decision and syndrome from the c2v the previous iteration left, then the layers in order, each on the c2v the layers
+			// before it have just written (one buffer; the launches of a stream run in order)
+			HIP_TRY(d, nbl_launch_vn_decide(d->g, d->w, c.r, st));
+			HIP_TRY(d, mark(c, 0, st));
+			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
+			HIP_TRY(d, mark(c, 1, st));
+			for (int l = 0; l < d->n_layers; l++)
+				HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
+			HIP_TRY(d, mark(c, 2, st));
+			if (count) { d->launches[0]++; d->launches[1]++; d->launches[2] += d->n_layers; }
+			continue;
+		}
 		if (c.fused) {
 			// one launch = variable-node pass + check-node pass; c2v ping-pongs between the two buffers
 			NblWork wf = d->w;
@@ -856,7 +1014,7 @@ static nbl_status run_window(IterCtx &c, int widx, int it_lo, int it_hi, hipStre
 		if (d->gexec[widx]) {
 			HIP_TRY(d, hipGraphLaunch(d->gexec[widx], st));
 			const int n = it_hi - it_lo + 1;
-			d->launches[1] += n; d->launches[2] += n;
+			d->launches[1] += n; d->launches[2] += d->layered ? (long long)n * d->n_layers : n;
 			if (!c.fused) d->launches[0] += n;
 			return NBL_OK;
 		}
@@ -1397,7 +1555,8 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 		else rc = grab(d->w.post + (size_t)b * N * q, nullptr, N, post);
 	}
 	if (!rc && v2c) {
-		if (!d->w.v2c) { d->err = "v2c is not kept in HBM on the fused path unless state recording is on (nbl_set_record_state)"; rc = NBL_ERR_ARG; }
+		if (d->layered) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
+		else if (!d->w.v2c) { d->err = "v2c is not kept in HBM on the fused path unless state recording is on (nbl_set_record_state)"; rc = NBL_ERR_ARG; }
 		else rc = grab(d->w.v2c + (size_t)b * E * q, nullptr, E, v2c);
 	}
 	if (!rc && c2v) {

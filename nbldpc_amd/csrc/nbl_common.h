@@ -60,6 +60,15 @@ struct NblWork {
 	unsigned long long *stamps;     // [16] debug: per-section cycle sums of the check-node kernel (NULL = off)
 };
 
+// layered (check-serial) schedule, nbl_create_layered (nbl_cn_layered.hip)
+#define NBL_LAYER_ROW 12
+struct NblLayerDev {
+	const int *chk;  // [M] the checks sorted by layer (ascending index inside a layer); layer l is chk[off[l]] .. chk[off[l + 1] - 1], the
+	                 // offsets stay on the host: one launch per layer gets (offset, count)
+	const int *nbr;  // [E][NBL_LAYER_ROW] per check-major edge, everything the input stage needs in one row: [0] its variable n,
+	                 // [1] n's degree dv, [4 .. 4 + dv - 1] the c2v slots (check-major positions) of n's edges in n's edge order
+};
+
 struct NblRun {
 	int B;                          // codeword slots the grid covers (= batch size unless w.active is set, then an upper bound of *w.n_act)
 	int iter, fixed_iters;

@@ -17,6 +17,11 @@ hipError_t nbl_launch_unpad(const double *src, double *dst, const int *map, int 
 size_t nbl_ems_lds_bytes(const NblGraphDev &g, int nm, int layers);
 int nbl_ems_layers(const NblGraphDev &g, int nc);
 
+// layered schedule for EMS (nbl_cn_layered.hip): decision + posterior without the v2c write, and the checks of one layer
+// (chk[offset] .. chk[offset + count - 1]), inputs formed from L_ch and the in-place c2v
+hipError_t nbl_launch_vn_decide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_ems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 bool nbl_ems256_applicable(const NblGraphDev &g, bool all_dc4, int nm, int nc);
 size_t nbl_ems256_lds_bytes(int nm);

@@ -1,8 +1,10 @@
 // nbldpc_amd/host/nbldpc_host.cpp -- see nbldpc_host.h.
 #include "nbldpc_host.h"
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <string>
 
 CNBLDPC::~CNBLDPC()
 {
@@ -70,8 +72,23 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	std::vector<uint8_t> gf_mat;
 	if (osd && !LoadMatRepr(gf_mat)) return false;
 	nbl_osd_params op = {sim.OSD_order, sim.OSD_flag, sim.OSD_factor, sim.crcLen, sim.crc_correctLen, gf_mat.data()};
-	nbl_status st = nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
-	                               osd ? &op : nullptr, device, &dec);
+	// NBL_SCHEDULE=layered: the layered (check-serial) schedule with the library's greedy layers in place of flooding (off by default;
+	// EMS without OSD only -- nbl_create_layered says why)
+	const char *sched = getenv("NBL_SCHEDULE");
+	const bool layered = sched && std::string(sched) == "layered";
+	if (sched && !layered && std::string(sched) != "flooding") {
+		error = std::string("NBL_SCHEDULE=") + sched + ": unknown schedule (flooding, layered)";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (layered && osd) {
+		error = "NBL_SCHEDULE=layered: the layered schedule is defined for EMS (method 2) without OSD only";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	nbl_status st = layered ? nbl_create_layered(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
+	                        : nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
+	                                         osd ? &op : nullptr, device, &dec);
 	if (st != NBL_OK) {
 		error = nbl_last_error(nullptr);
 		std::cerr << error << std::endl; // the reference prints and exits for its own configuration errors (NBLDPC.cpp:284-285)
