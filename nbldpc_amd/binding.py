@@ -17,7 +17,7 @@ METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
@@ -83,6 +83,8 @@ def load_library():
         L.nbl_layer_greedy.argtypes = [C.POINTER(CodeDesc), C.c_void_p]
         L.nbl_create_layered.restype = C.c_int
         L.nbl_create_layered.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_create_layered_ex.restype = C.c_int
+        L.nbl_create_layered_ex.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_get_layers.restype = C.c_int
         L.nbl_get_layers.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.nbl_destroy.argtypes = [C.c_void_p]
@@ -143,12 +145,14 @@ class Decoder:
     of methods 1/2/4/7 with osd_order >= 0) takes osd_* / crc_len / crc_rows / gf_mat through nbl_create_osd; with osd_order=None the
     handle is made as before, so method 6 is refused.  gf_mat=None: the GF element matrices as the reference's loader leaves them
     (datafiles.gf_matrices(q, as_loaded=True)).  layers: None = the flooding schedule; "greedy" or an int array [M] (a layer per
-    check) = the layered schedule through nbl_create_layered (EMS only; no bs_* / osd_* parameters go with it)."""
+    check) = the layered schedule through nbl_create_layered (EMS only; no bs_* / osd_* parameters go with it).  damped (with layers
+    only): None = nbl_create_layered as before; anything else goes through nbl_create_layered_ex with flags = int(damped), so True =
+    NBL_LAYERED_DAMPED: T-EMS under the layered schedule with its per-edge damping (inert for EMS), False = flags 0."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None, layers=None):
+                 gf_mat=None, layers=None, damped=None):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -158,14 +162,20 @@ class Decoder:
                              tems_offset, fixed_iters, poll_every, max_batch)
         desc = code.desc()
         h = C.c_void_p()
+        if damped is not None and layers is None:
+            raise ValueError("damped: the flag belongs to the layered schedule (give layers='greedy' or an assignment)")
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
                 raise ValueError("layers: nbl_create_layered takes neither OSD nor extension parameters")
             self._layer_of = None if isinstance(layers, str) and layers == "greedy" else np.ascontiguousarray(layers, dtype=np.int32)
             if self._layer_of is not None and self._layer_of.shape != (code.M,):
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
-            rc = self.lib.nbl_create_layered(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params),
-                                             None if self._layer_of is None else self._layer_of.ctypes.data, device, C.byref(h))
+            lay = None if self._layer_of is None else self._layer_of.ctypes.data
+            if damped is None:
+                rc = self.lib.nbl_create_layered(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
+            else:
+                rc = self.lib.nbl_create_layered_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,
+                                                    int(damped), device, C.byref(h))
         elif osd_order is not None:
             self._gf_mat = np.ascontiguousarray(datafiles.gf_matrices(code.q) if gf_mat is None else gf_mat, dtype=np.uint8)
             self.osd = OsdParams(osd_order, osd_flag, osd_factor, crc_len, crc_rows, self._gf_mat.ctypes.data)
@@ -375,7 +385,7 @@ class Decoder:
         return list(ms), list(ln)
 
     def read_state(self, b, post=True, v2c=True):
-        """(post, v2c, c2v) of codeword b; post=False / v2c=False pass NULL and return None in that place (a layered decoder has no v2c)"""
+        """(post, v2c, c2v) of codeword b; post=False / v2c=False pass NULL and return None in that place (a layered EMS decoder has no v2c)"""
         w, N, E = self.code.q - 1, self.code.N, self.code.E
         P = np.zeros((N, w)) if post else None
         V = np.zeros((E, w)) if v2c else None

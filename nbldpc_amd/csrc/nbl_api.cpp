@@ -46,7 +46,8 @@ struct nbl_decoder {
 	                            // have to be cleared on every call)
 	const double *last_c2v = nullptr;
 	bool last_fused = false;    // the last decode ran fused iterations (nbl_read_state picks the c2v buffer per codeword)
-	// layered (check-serial) schedule (nbl_create_layered): EMS only, one c2v buffer updated in place, no v2c
+	// layered (check-serial) schedule (nbl_create_layered / nbl_create_layered_ex): one c2v buffer updated in place; EMS keeps no v2c,
+	// T-EMS (NBL_LAYERED_DAMPED) keeps the per-edge v2c its damping reads, updated in place by the edge's check
 	bool layered = false;
 	int n_layers = 0;
 	std::vector<int> h_layer_of; // [M] the assignment in use
@@ -226,7 +227,8 @@ static nbl_status ensure_workspace(nbl_decoder *d, int B)
 {
 	// v2c only exists in HBM when something reads it: the unfused path, or state read-back
 	// (damped methods always keep it: the damping reads the previous iteration's v2c)
-	const bool want_v2c = !d->layered && (d->prm.method != NBL_METHOD_EMS || !fused_shape(d) || d->record_state || d->force_generic != 0);
+	const bool want_v2c = d->layered ? d->prm.method == NBL_METHOD_TEMS
+	                                 : (d->prm.method != NBL_METHOD_EMS || !fused_shape(d) || d->record_state || d->force_generic != 0);
 	const bool want_post = d->record_state || d->osd_acc;
 	if (B <= d->cap && (!want_post || d->w.post) && (!want_v2c || d->w.v2c)) return NBL_OK;
 	int cap = B > d->cap ? B : d->cap;
@@ -491,8 +493,8 @@ extern "C" int32_t nbl_layer_greedy(const nbl_code_desc *code, int32_t *layer_of
 	return layer_greedy(N, M, coff, code->chk_var, layer_of);
 }
 
-// nbl_create_layered's request: layer_of == NULL asks for the greedy assignment
-struct LayerReq { const int32_t *layer_of; };
+// nbl_create_layered's / nbl_create_layered_ex's request: layer_of == NULL asks for the greedy assignment; flags: NBL_LAYERED_*
+struct LayerReq { const int32_t *layer_of; uint32_t flags; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out);
@@ -506,7 +508,14 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 extern "C" nbl_status nbl_create_layered(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                          const int32_t *layer_of, int device, nbl_decoder **out)
 {
-	const LayerReq lay = {layer_of};
+	const LayerReq lay = {layer_of, 0};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
+}
+
+extern "C" nbl_status nbl_create_layered_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                            const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	const LayerReq lay = {layer_of, flags};
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
 }
 
@@ -524,6 +533,8 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
 	if (!code || !gf_mul || !gf_inv || !params) return fail_create(nullptr, NBL_ERR_ARG, "null argument");
+	if (lay && (lay->flags & ~(uint32_t)NBL_LAYERED_DAMPED))
+		return fail_create(nullptr, NBL_ERR_ARG, "layered schedule: unknown flag bit (flags = " + std::to_string(lay->flags) + "; NBL_LAYERED_DAMPED = 1 is the only one defined)");
 	const int N = code->N, M = code->M, q = code->q;
 	if (N <= 0 || M <= 0 || q < 4 || (q & (q - 1))) return fail_create(nullptr, NBL_ERR_ARG, "N, M must be positive and q a power of two, at least 4");
 	// (the reference ships arithmetic tables up to GF(512) but no code above GF(256); a valid request this library cannot serve)
@@ -531,7 +542,10 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	std::string field_err;
 	const int poly = validate_field(q, gf_mul, gf_inv, field_err);
 	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
-	if (lay && params->method != NBL_METHOD_EMS)
+	if (lay && (lay->flags & NBL_LAYERED_DAMPED) && params->method != NBL_METHOD_EMS && params->method != NBL_METHOD_TEMS)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the damped layered schedule (NBL_LAYERED_DAMPED) is defined for T-EMS (method 4), and for EMS (method 2), which "
+		                                                 "has no damping, as the plain layered schedule: log-QSPA (method 1) and BS-TEMS (method 7) stay flooding-only");
+	if (lay && params->method != NBL_METHOD_EMS && !((lay->flags & NBL_LAYERED_DAMPED) && params->method == NBL_METHOD_TEMS))
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the layered schedule is defined for EMS (method 2) only: the other methods damp against the previous iteration's "
 		                                                 "decision in their variable-node pass and stay flooding-only");
 	switch (params->method) {
@@ -655,10 +669,15 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	int n_layers = 0;
 	if (lay) {
 		// (the layered kernel is the general one: no specialised shape stands in for it, so the LDS bound holds for every shape)
-		const int dl = (params->ems_nc >= maxdc - 1) ? 1 : params->ems_nc + 1;
-		const size_t lds = ((size_t)maxdc * q + (2 * (size_t)dl + 1) * q + (size_t)maxdc * params->ems_nm) * 8 + (size_t)maxdc * params->ems_nm * 4 + 16;
-		if (lds > 160 * 1024)
-			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
+		if (params->method == NBL_METHOD_TEMS) {
+			if (nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
+				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");
+		} else {
+			const int dl = (params->ems_nc >= maxdc - 1) ? 1 : params->ems_nc + 1;
+			const size_t lds = ((size_t)maxdc * q + (2 * (size_t)dl + 1) * q + (size_t)maxdc * params->ems_nm) * 8 + (size_t)maxdc * params->ems_nm * 4 + 16;
+			if (lds > 160 * 1024)
+				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
+		}
 		layer_of.assign(M, 0);
 		if (lay->layer_of) {
 			std::string lerr;
@@ -938,8 +957,11 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			HIP_TRY(d, mark(c, 0, st));
 			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
 			HIP_TRY(d, mark(c, 1, st));
-			for (int l = 0; l < d->n_layers; l++)
-				HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
+			// (T-EMS: each check also damps its inputs against the v2c buffer and updates it in place; init_kernel has set v2c = L_ch)
+			for (int l = 0; l < d->n_layers; l++) {
+				if (p.method == NBL_METHOD_TEMS) HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
+				else HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
+			}
 			HIP_TRY(d, mark(c, 2, st));
 			if (count) { d->launches[0]++; d->launches[1]++; d->launches[2] += d->n_layers; }
 			continue;
@@ -1555,7 +1577,7 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 		else rc = grab(d->w.post + (size_t)b * N * q, nullptr, N, post);
 	}
 	if (!rc && v2c) {
-		if (d->layered) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
+		if (d->layered && d->prm.method != NBL_METHOD_TEMS) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
 		else if (!d->w.v2c) { d->err = "v2c is not kept in HBM on the fused path unless state recording is on (nbl_set_record_state)"; rc = NBL_ERR_ARG; }
 		else rc = grab(d->w.v2c + (size_t)b * E * q, nullptr, E, v2c);
 	}

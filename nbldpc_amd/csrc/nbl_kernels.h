@@ -22,6 +22,12 @@ int nbl_ems_layers(const NblGraphDev &g, int nc);
 hipError_t nbl_launch_vn_decide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_ems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// damped layered schedule for T-EMS (nbl_cn_tems_layered.hip): the checks of one layer; each forms its inputs from L_ch and the in-place
+// c2v, damps them against the edge's stored v2c (w.v2c, updated in place) and runs the programme of nbl_cn_tems_core.h.  LDS: the
+// larger of the two programmes a launch may take (pure arithmetic: nbl_create_layered_ex refuses above 160 KB before the device)
+size_t nbl_tems_layered_lds_bytes(int q, int maxdc, int nc);
+hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 bool nbl_ems256_applicable(const NblGraphDev &g, bool all_dc4, int nm, int nc);
 size_t nbl_ems256_lds_bytes(int nm);
@@ -29,6 +35,7 @@ hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const Nb
 
 // T-EMS and log-QSPA check nodes (nbl_cn_tems.hip, nbl_cn_bp.hip)
 hipError_t nbl_launch_cn_tems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+bool nbl_tems_use_fast(int nc); // the fast programme (nc <= 3) unless NBL_TEMS_GENERIC is set (A/B runs)
 hipError_t nbl_launch_cn_bp(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 
 // small fields (q <= 32), 64 / q checks per wave (nbl_cn_small.hip); method as in include/nbldpc.h (1 BP, 2 EMS, 4 T-EMS)

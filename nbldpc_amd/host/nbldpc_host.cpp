@@ -73,22 +73,26 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	if (osd && !LoadMatRepr(gf_mat)) return false;
 	nbl_osd_params op = {sim.OSD_order, sim.OSD_flag, sim.OSD_factor, sim.crcLen, sim.crc_correctLen, gf_mat.data()};
 	// NBL_SCHEDULE=layered: the layered (check-serial) schedule with the library's greedy layers in place of flooding (off by default;
-	// EMS without OSD only -- nbl_create_layered says why)
+	// EMS without OSD only -- nbl_create_layered says why).  NBL_SCHEDULE=layered-damped: the same through nbl_create_layered_ex with
+	// NBL_LAYERED_DAMPED, which also serves T-EMS (its per-edge damping done by the check) and leaves EMS as it is; no OSD either
 	const char *sched = getenv("NBL_SCHEDULE");
-	const bool layered = sched && std::string(sched) == "layered";
+	const bool damped = sched && std::string(sched) == "layered-damped";
+	const bool layered = damped || (sched && std::string(sched) == "layered");
 	if (sched && !layered && std::string(sched) != "flooding") {
-		error = std::string("NBL_SCHEDULE=") + sched + ": unknown schedule (flooding, layered)";
+		error = std::string("NBL_SCHEDULE=") + sched + ": unknown schedule (flooding, layered, layered-damped)";
 		std::cerr << error << std::endl;
 		return false;
 	}
 	if (layered && osd) {
-		error = "NBL_SCHEDULE=layered: the layered schedule is defined for EMS (method 2) without OSD only";
+		error = damped ? "NBL_SCHEDULE=layered-damped: the damped layered schedule is defined for T-EMS (method 4) and EMS (method 2) without OSD only"
+		               : "NBL_SCHEDULE=layered: the layered schedule is defined for EMS (method 2) without OSD only";
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = layered ? nbl_create_layered(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
-	                        : nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
-	                                         osd ? &op : nullptr, device, &dec);
+	nbl_status st = damped    ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
+	                : layered ? nbl_create_layered(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
+	                          : nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
+	                                           osd ? &op : nullptr, device, &dec);
 	if (st != NBL_OK) {
 		error = nbl_last_error(nullptr);
 		std::cerr << error << std::endl; // the reference prints and exits for its own configuration errors (NBLDPC.cpp:284-285)

@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
-"""Flooding against the layered schedule on config 3, end to end with early exit (a number to record, not to assert).
+"""Flooding against the layered schedule, end to end with early exit (a number to record, not to assert).
 
-U512.256 GF(256), EMS nm = 32 nc = 3, max_iter 50, early exit with the harness's poll_every (2), batch 4096.  The frames are the
+--method ems (default): config 3's shape, U512.256 GF(256), EMS nm = 32 nc = 3, against nbl_create_layered.
+--method tems: config 4's shape, BDS576.288 GF(64), T-EMS nr = 2 nc = 3, against the damped layered schedule (nbl_create_layered_ex
+with NBL_LAYERED_DAMPED).
+max_iter 50, early exit with the harness's poll_every (2), batch 4096.  The frames are the
 host link chain's own (random message, CRC, encoder, BPSK, AWGN: hostlib.frontend, `batch` lanes, one frame each), the SAME LLRs for
 both schedules, resident in HBM.  Per Eb/N0 and schedule: mean iterations per frame, frame errors (decoded word != transmitted
 word), ms per iteration (batch time / iterations launched) and frames per second; one warm-up decode, then the median of `repeats`
 timed ones (wall clock around a synchronised call).
 
-usage: python tools/layered_vs_flooding.py [batch] [repeats] [EbN0 ...]   -- one JSON line per (Eb/N0, schedule), then a table"""
+usage: python tools/layered_vs_flooding.py [--method ems|tems] [batch] [repeats] [EbN0 ...]
+-- one JSON line per (Eb/N0, schedule), then a table"""
 import json
 import os
 import statistics
@@ -23,25 +27,31 @@ import nbldpc_amd as nb  # noqa: E402
 from nbldpc_amd import hostlib  # noqa: E402
 from nbldpc_amd.profiles import DEFAULTS  # noqa: E402
 
-CODE = "divsalar.UNBLDPC.512.256.GF.256"
-KW = dict(ems_nm=32, ems_nc=3)
+# method switch -> (code, nbl method, its parameters, the layered decoder's extra arguments, its name in the table)
+SHAPES = {"ems": ("divsalar.UNBLDPC.512.256.GF.256", nb.METHOD_EMS, dict(ems_nm=32, ems_nc=3), dict(layers="greedy"), "layered"),
+          "tems": ("BDS.576.288.GF.64", nb.METHOD_TEMS, dict(tems_nr=2, tems_nc=3), dict(layers="greedy", damped=True), "layered-damped")}
 MAX_ITER, POLL = 50, 2
 
 
-def frames(workdir, ebn0, B, code):
-    prof = dict(DEFAULTS, gfq=code.q, method=nb.METHOD_EMS, max_iter=MAX_ITER, parallel=B, **KW)
+def frames(workdir, ebn0, B, code, name, method, kw):
+    prof = dict(DEFAULTS, gfq=code.q, method=method, max_iter=MAX_ITER, parallel=B, **kw)
     prof = {k: v for k, v in prof.items() if k not in ("code", "constellation")}
-    hostlib.prepare_workdir(workdir, dict(prof, code=CODE), CODE, "BPSK")
+    hostlib.prepare_workdir(workdir, dict(prof, code=name), name, "BPSK")
     L, tx, _, _ = hostlib.frontend(workdir, ebn0, 1, code.N, code.N - code.M, code.q, B)
     return L, tx
 
 
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-    repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    points = [float(x) for x in sys.argv[3:]] or [1.0, 1.5, 2.0]
+    argv = sys.argv[1:]
+    which = "ems"
+    if argv and argv[0] == "--method":
+        which, argv = argv[1], argv[2:]
+    name, method, kw, lay_kw, lay_name = SHAPES[which]
+    B = int(argv[0]) if len(argv) > 0 else 4096
+    repeats = int(argv[1]) if len(argv) > 1 else 5
+    points = [float(x) for x in argv[2:]] or [1.0, 1.5, 2.0]
     dev = torch.device("cuda", 0)
-    code = nb.Code(CODE)
+    code = nb.Code(name)
     out = torch.zeros((B, code.N), dtype=torch.int32, device=dev)
     conv = torch.zeros(B, dtype=torch.uint8, device=dev)
     its = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -49,12 +59,11 @@ def main():
     rows = []
     for ebn0 in points:
         with tempfile.TemporaryDirectory() as tmp:
-            L, tx = frames(tmp, ebn0, B, code)
+            L, tx = frames(tmp, ebn0, B, code, name, method, kw)
         dL = torch.from_numpy(L).to(dev).contiguous()
         del L
-        for sched in ("flooding", "layered"):
-            dec = nb.Decoder(code, nb.METHOD_EMS, MAX_ITER, poll_every=POLL, max_batch=B, device=0,
-                             layers="greedy" if sched == "layered" else None, **KW)
+        for sched in ("flooding", lay_name):
+            dec = nb.Decoder(code, method, MAX_ITER, poll_every=POLL, max_batch=B, device=0, **(lay_kw if sched != "flooding" else {}), **kw)
             times = []
             for k in range(repeats + 1):  # (the first one warms up: workspace, code objects, clocks)
                 torch.cuda.synchronize()
@@ -66,7 +75,7 @@ def main():
             _, launches = dec.last_timing()
             dt = statistics.median(times)
             ferr = int((out.cpu().numpy() != tx).any(axis=1).sum())
-            row = dict(ebn0=ebn0, schedule=sched, batch=B, n_layers=(int(dec.layers.max()) + 1 if sched == "layered" else 1),
+            row = dict(ebn0=ebn0, schedule=sched, batch=B, method=which, n_layers=(int(dec.layers.max()) + 1 if sched != "flooding" else 1),
                        iterations_per_frame=float(its.double().mean().item()), frame_errors=ferr, not_converged=int(B - conv.sum().item()),
                        iterations_launched=int(launches[1]), ms_per_iteration=dt * 1e3 / max(int(launches[1]), 1), ms_per_batch=dt * 1e3,
                        frames_per_s=B / dt, spread_ms=[min(times) * 1e3, max(times) * 1e3])
