@@ -139,6 +139,29 @@ def layer_greedy(code):
     return layer_of
 
 
+class PlanInfo(C.Structure):
+    _fields_ = [("cn", C.c_char_p), ("fusable", C.c_int32), ("fused", C.c_int32), ("want_v2c", C.c_int32)]
+
+
+def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=None, bs_nc=2, layers=None, damped=None,
+               force_generic=0, record_state=False):
+    """The check-node kernel a decoder of this description would run (nbl_debug_plan; host arithmetic, no device, no decoder):
+    (kernel name, fusable, fused, want_v2c).  The description is built the way Decoder builds it; layers / damped as there
+    (None = flooding), force_generic as nbl_debug_force_generic takes it, record_state as nbl_set_record_state."""
+    lib = load_library()
+    params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
+    ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
+    desc = code.desc()
+    out = PlanInfo()
+    lib.nbl_debug_plan.restype = C.c_int
+    lib.nbl_debug_plan.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.POINTER(ParamsExt), C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
+    rc = lib.nbl_debug_plan(C.byref(desc), C.byref(params), C.byref(ext) if ext is not None else None,
+                            -1 if layers is None else int(bool(damped)), force_generic, int(record_state), C.byref(out))
+    if rc != 0:
+        raise NblError(rc, "nbl_debug_plan")
+    return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
+
+
 class Decoder:
     """Batched decoder handle (nbl_create .. nbl_destroy).  Basic-set T-EMS (method 7) takes bs_nm / bs_nc / bs_factor / bs_offset
     through nbl_create_ex; without bs_nm the handle is made by nbl_create, which refuses method 7.  OSD (method 6, or post-processing

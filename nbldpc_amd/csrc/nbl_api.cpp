@@ -37,9 +37,7 @@ struct nbl_decoder {
 	uint8_t *d_conv8 = nullptr;
 	hipStream_t stream = nullptr;
 	bool record_state = false;
-	bool all_dc4 = false;       // every check has degree 4
-	int min_dc = 0;             // smallest check degree
-	bool all_dv2 = false;       // every variable has degree 2
+	NblShape shape{};           // what the kernel choice depends on (nbl_plan.h)
 	double *c2v_alt = nullptr;  // second c2v buffer of the fused EMS iteration (flooding schedule -> double buffer)
 	double *c2v_zero = nullptr; // fused iterations: the all-zero c2v of iteration 0, ONE [E][q] block shared by all codewords, written once
 	                            // when the workspace is made and only ever read (iteration 1 reads it instead of a buffer that would
@@ -183,52 +181,22 @@ static void free_workspace(nbl_decoder *d)
 	d->ws_bytes = 0;
 }
 
-// Shapes whose whole iteration is ONE launch (variable-node pass recomputed inside the check-node kernel, c2v double-buffered):
-// (2,4)-regular codes, EMS over GF(256) with nm <= 64, T-EMS over GF(64) and GF(256), log-QSPA over GF(256).
 static bool small_enabled()
 {
-	static const bool on = !getenv("NBL_NO_SMALL"); // A/B measurements: the one-check-per-wave kernels on small fields
+	static const bool on = !getenv("NBL_NO_SMALL"); // A/B measurements: the several-checks-per-wave kernels on small fields
 	return on;
 }
 
-// small fields (q <= 64): 64 / q checks per wave, any variable degree (nbl_cn_small.hip)
-static bool small_shape(const nbl_decoder *d)
+// The kernel choice of this decoder as it stands (nbl_plan.cpp): once per workspace check and once per decode, never per launch
+static NblPlan plan_of(const nbl_decoder *d)
 {
-	if (!small_enabled()) return false;
-	const nbl_params &p = d->prm;
-	// (GF(64), check degree 4, T-EMS has its own kernel: config 4)
-	if (p.method == NBL_METHOD_TEMS && d->all_dv2 && nbl_tems64_applicable(d->g, d->all_dc4, p.tems_nr, p.tems_nc)) return false;
-	if (p.method == NBL_METHOD_BP && nbl_bp64_applicable(d->g, d->all_dc4)) return false; // (and log-QSPA: nbl_cn_bp64.hip)
-	if (p.method == NBL_METHOD_EMS) return nbl_small_applicable(d->g, p.method, d->min_dc, p.ems_nm, p.ems_nc);
-	if (p.method == NBL_METHOD_TEMS) return nbl_small_applicable(d->g, p.method, d->min_dc, 0, p.tems_nc);
-	if (p.method == NBL_METHOD_BP) return nbl_small_applicable(d->g, p.method, d->min_dc, 0, 0);
-	return false;
-}
-
-static bool ems64_shape(const nbl_decoder *d)
-{
-	return small_enabled() && d->prm.method == NBL_METHOD_EMS && nbl_ems64_applicable(d->g, d->min_dc, d->prm.ems_nm, d->prm.ems_nc);
-}
-
-static bool fused_shape(const nbl_decoder *d)
-{
-	if (d->layered) return false; // (the fused kernels ARE the flooding schedule: c2v double-buffered)
-	// (variable degrees above 3: these kernels behind the separate VN pass)
-	if (small_shape(d) || ems64_shape(d)) return d->g.c_nbr != nullptr;
-	if (!d->all_dv2) return false;
-	if (d->prm.method == NBL_METHOD_EMS) return nbl_ems256_applicable(d->g, d->all_dc4, d->prm.ems_nm, d->prm.ems_nc);
-	if (d->prm.method == NBL_METHOD_TEMS)
-		return nbl_tems64_applicable(d->g, d->all_dc4, d->prm.tems_nr, d->prm.tems_nc) || nbl_tems256_applicable(d->g, d->all_dc4, d->prm.tems_nr, d->prm.tems_nc);
-	if (d->prm.method == NBL_METHOD_BP) return nbl_bp256_applicable(d->g, d->all_dc4) || nbl_bp64_applicable(d->g, d->all_dc4);
-	return false;
+	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled());
 }
 
 static nbl_status ensure_workspace(nbl_decoder *d, int B)
 {
-	// v2c only exists in HBM when something reads it: the unfused path, or state read-back
-	// (damped methods always keep it: the damping reads the previous iteration's v2c)
-	const bool want_v2c = d->layered ? d->prm.method == NBL_METHOD_TEMS
-	                                 : (d->prm.method != NBL_METHOD_EMS || !fused_shape(d) || d->record_state || d->force_generic != 0);
+	const NblPlan plan = plan_of(d);
+	const bool want_v2c = plan.want_v2c;
 	const bool want_post = d->record_state || d->osd_acc;
 	if (B <= d->cap && (!want_post || d->w.post) && (!want_v2c || d->w.v2c)) return NBL_OK;
 	int cap = B > d->cap ? B : d->cap;
@@ -239,7 +207,7 @@ static nbl_status ensure_workspace(nbl_decoder *d, int B)
 	HIP_TRY(d, alloc((void **)&d->w.Lch, (size_t)cap * N * q * 8));
 	if (want_v2c) HIP_TRY(d, alloc((void **)&d->w.v2c, (size_t)cap * E * q * 8));
 	HIP_TRY(d, alloc((void **)&d->w.c2v, (size_t)cap * E * q * 8));
-	if (fused_shape(d)) {
+	if (plan.fusable) { // (whatever force_generic says: nbl_workspace_bytes does not move with a debug switch)
 		HIP_TRY(d, alloc((void **)&d->c2v_alt, (size_t)cap * E * q * 8));
 		HIP_TRY(d, alloc((void **)&d->c2v_zero, E * q * 8)); // one block for every codeword (NblWork::c2v_prev_shared)
 		HIP_TRY(d, hipMemset(d->c2v_zero, 0, E * q * 8));
@@ -616,16 +584,15 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 
 	// ---- host-side graph indices (NBLDPC.cpp:236-263) -------------------------------------------------------
 	std::vector<int> voff(N + 1, 0), coff(M + 1, 0);
-	int maxdv = 0, maxdc = 0;
+	const NblShape shape = nbl_shape(code);
+	const int maxdv = shape.maxdv, maxdc = shape.maxdc, p = shape.p;
 	for (int n = 0; n < N; n++) {
 		if (code->var_deg[n] < 1) return fail_create(nullptr, NBL_ERR_ARG, "variable of degree < 1");
 		voff[n + 1] = voff[n] + code->var_deg[n];
-		if (code->var_deg[n] > maxdv) maxdv = code->var_deg[n];
 	}
 	for (int m = 0; m < M; m++) {
 		if (code->chk_deg[m] < 2) return fail_create(nullptr, NBL_ERR_ARG, "check of degree < 2");
 		coff[m + 1] = coff[m] + code->chk_deg[m];
-		if (code->chk_deg[m] > maxdc) maxdc = code->chk_deg[m];
 	}
 	const int E = voff[N];
 	if (coff[M] != E) return fail_create(nullptr, NBL_ERR_ARG, "variable-side and check-side edge counts differ");
@@ -653,17 +620,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 				if (code->var_chk[e] == m) c_epos[ce] = e; // like ChkLinkDv
 			if (c_epos[ce] < 0) return fail_create(nullptr, NBL_ERR_ARG, "check-side edge without variable-side partner");
 		}
-	const int p = ilog2(q);
 	// shape limits of the kernels, refused here rather than at the first decode
 	if (params->method == NBL_METHOD_TEMS && p * maxdc > 32)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: log2(q) * (largest check degree) must not exceed 32 (the trellis path code is one 32-bit word)");
-	if (params->method == NBL_METHOD_EMS) {
-		const int layers = (params->ems_nc >= maxdc - 1) ? 1 : params->ems_nc + 1;
-		const size_t lds = ((size_t)maxdc * q + (2 * (size_t)layers + 1) * q + (size_t)maxdc * params->ems_nm) * 8 + (size_t)maxdc * params->ems_nm * 4 + 16;
-		const bool special = q == 256 && maxdc == 4 && params->ems_nc >= 1 && params->ems_nm <= 64;
-		if (!special && lds > 160 * 1024)
-			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
-	}
+	if (params->method == NBL_METHOD_EMS && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
 	// ---- layered schedule: the assignment, checked or made here, before the device is touched ----
 	std::vector<int> layer_of, lay_off, lay_chk, lay_nbr;
 	int n_layers = 0;
@@ -672,11 +633,8 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		if (params->method == NBL_METHOD_TEMS) {
 			if (nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");
-		} else {
-			const int dl = (params->ems_nc >= maxdc - 1) ? 1 : params->ems_nc + 1;
-			const size_t lds = ((size_t)maxdc * q + (2 * (size_t)dl + 1) * q + (size_t)maxdc * params->ems_nm) * 8 + (size_t)maxdc * params->ems_nm * 4 + 16;
-			if (lds > 160 * 1024)
-				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
+		} else if (nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
+			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
 		}
 		layer_of.assign(M, 0);
 		if (lay->layer_of) {
@@ -742,13 +700,8 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;
-	d->all_dc4 = true;
-	for (int m = 0; m < M; m++) d->all_dc4 = d->all_dc4 && (code->chk_deg[m] == 4);
-	d->min_dc = code->chk_deg[0];
-	for (int m = 0; m < M; m++) d->min_dc = code->chk_deg[m] < d->min_dc ? code->chk_deg[m] : d->min_dc;
-	d->all_dv2 = true;
-	for (int n = 0; n < N; n++) d->all_dv2 = d->all_dv2 && (code->var_deg[n] == 2);
-	if (q == 256 && d->all_dc4) {
+	d->shape = shape;
+	if (shape.has_ems_toff()) {
 		// permutation offsets of the specialised EMS kernel: variable-domain symbol a of lane l -> byte offset of h*a in a q-vector
 		std::vector<unsigned long long> toff((size_t)E * 64);
 		for (int ce = 0; ce < E; ce++)
@@ -762,7 +715,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 			}
 		if ((st = upload(d, toff, &d->g.ems_toff))) return fail_create(d, st, "");
 	}
-	if (d->all_dc4 && d->all_dv2) {
+	if (shape.has_dv2_row()) {
 		std::vector<int> row((size_t)M * 16);
 		for (int m = 0; m < M; m++)
 			for (int j = 0; j < 4; j++) {
@@ -774,9 +727,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 			}
 		if ((st = upload(d, row, &d->g.dv2_row))) return fail_create(d, st, "");
 	}
-	int mindv = maxdv;
-	for (int n = 0; n < N; n++) mindv = code->var_deg[n] < mindv ? code->var_deg[n] : mindv;
-	if (q <= 64 && maxdv <= 3 && mindv >= 2) {
+	if (shape.has_c_nbr()) {
 		// fused small-field iteration: everything the variable-node stage of a check-major edge needs, in one 16-byte row
 		// (variable degrees 2 and 3 only: the fused loaders add the second c2v vector unconditionally; a code with a degree-1
 		// variable takes the separate variable-node launch, which handles any degree)
@@ -890,29 +841,37 @@ extern "C" nbl_status nbl_last_timing(nbl_decoder *d, double ms[4], int64_t laun
 	return NBL_OK;
 }
 
-static nbl_status launch_cn(nbl_decoder *d, const NblRun &r, hipStream_t st)
+// Diagnostic only (not part of include/nbldpc.h): the kernel choice for a code description -- the shape and the plan, nothing else;
+// no device, no decoder, no field tables.  layered_flags: NBL_LAYERED_* of nbl_create_layered_ex, -1 = the flooding schedule.
+struct nbl_plan_info { const char *cn; int32_t fusable, fused, want_v2c; };
+extern "C" nbl_status nbl_debug_plan(const nbl_code_desc *code, const nbl_params *params, const nbl_params_ext *ext, int32_t layered_flags,
+                                     int32_t force_generic, int32_t record_state, nbl_plan_info *out)
 {
-	const bool small_on = small_shape(d);
-	switch (d->prm.method) {
-	case NBL_METHOD_EMS:
-		if (d->force_generic != 1 && nbl_ems256_applicable(d->g, d->all_dc4, r.nm, r.nc)) HIP_TRY(d, nbl_launch_cn_ems256(d->g, d->w, r, false, st));
-		else if (d->force_generic != 1 && small_on) HIP_TRY(d, nbl_launch_cn_ems_small(d->g, d->w, r, false, st));
-		else if (d->force_generic != 1 && ems64_shape(d)) HIP_TRY(d, nbl_launch_cn_ems64(d->g, d->w, r, false, st));
-		else HIP_TRY(d, nbl_launch_cn_ems(d->g, d->w, r, st));
-		break;
-	case NBL_METHOD_TEMS:
-		if (d->force_generic != 1 && nbl_tems64_applicable(d->g, d->all_dc4, r.nr, r.nc)) HIP_TRY(d, nbl_launch_cn_tems64(d->g, d->w, r, false, st));
-		else if (d->force_generic != 1 && nbl_tems256_applicable(d->g, d->all_dc4, r.nr, r.nc)) HIP_TRY(d, nbl_launch_cn_tems256(d->g, d->w, r, false, st));
-		else if (d->force_generic != 1 && small_on) HIP_TRY(d, nbl_launch_cn_tems_small(d->g, d->w, r, false, st));
-		else HIP_TRY(d, nbl_launch_cn_tems(d->g, d->w, r, st));
-		break;
-	case NBL_METHOD_BP:
-		if (d->force_generic != 1 && nbl_bp256_applicable(d->g, d->all_dc4)) HIP_TRY(d, nbl_launch_cn_bp256(d->g, d->w, r, false, st));
-		else if (d->force_generic != 1 && nbl_bp64_applicable(d->g, d->all_dc4)) HIP_TRY(d, nbl_launch_cn_bp64(d->g, d->w, r, false, st));
-		else if (d->force_generic != 1 && small_on) HIP_TRY(d, nbl_launch_cn_bp_small(d->g, d->w, r, false, st));
-		else HIP_TRY(d, nbl_launch_cn_bp(d->g, d->w, r, st));
-		break;
-	case NBL_METHOD_BS_TEMS: HIP_TRY(d, nbl_launch_cn_bstems(d->g, d->w, r, st)); break;
+	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
+	const NblPlan plan = nbl_plan(nbl_shape(code), *params, ext ? *ext : nbl_params_ext{}, layered_flags >= 0, force_generic, record_state != 0, small_enabled());
+	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
+	return NBL_OK;
+}
+
+// The one launch of check-node kernel `cn`; fused: with the variable-node pass inside (w then carries c2v_prev).  The layered kernels
+// run once per layer and are launched where the layers are walked (enqueue_window).
+static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
+{
+	const NblGraphDev &g = d->g;
+	switch (cn) {
+	case NBL_CN_EMS256: HIP_TRY(d, nbl_launch_cn_ems256(g, w, r, fused, st)); break;
+	case NBL_CN_EMS_SMALL: HIP_TRY(d, nbl_launch_cn_ems_small(g, w, r, fused, st)); break;
+	case NBL_CN_EMS64: HIP_TRY(d, nbl_launch_cn_ems64(g, w, r, fused, st)); break;
+	case NBL_CN_EMS: HIP_TRY(d, nbl_launch_cn_ems(g, w, r, st)); break;
+	case NBL_CN_TEMS64: HIP_TRY(d, nbl_launch_cn_tems64(g, w, r, fused, st)); break;
+	case NBL_CN_TEMS256: HIP_TRY(d, nbl_launch_cn_tems256(g, w, r, fused, st)); break;
+	case NBL_CN_TEMS_SMALL: HIP_TRY(d, nbl_launch_cn_tems_small(g, w, r, fused, st)); break;
+	case NBL_CN_TEMS: HIP_TRY(d, nbl_launch_cn_tems(g, w, r, st)); break;
+	case NBL_CN_BP256: HIP_TRY(d, nbl_launch_cn_bp256(g, w, r, fused, st)); break;
+	case NBL_CN_BP64: HIP_TRY(d, nbl_launch_cn_bp64(g, w, r, fused, st)); break;
+	case NBL_CN_BP_SMALL: HIP_TRY(d, nbl_launch_cn_bp_small(g, w, r, fused, st)); break;
+	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
+	case NBL_CN_BSTEMS: HIP_TRY(d, nbl_launch_cn_bstems(g, w, r, st)); break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
 	return NBL_OK;
@@ -924,8 +883,9 @@ static nbl_status launch_cn(nbl_decoder *d, const NblRun &r, hipStream_t st)
 // of the time).
 struct IterCtx {
 	nbl_decoder *d;
+	NblPlan plan;
 	NblRun r;
-	bool damp, fused;
+	bool damp;
 	double *bufA, *bufB;
 	const double *zeros = nullptr; // stands in for bufA in iteration 1 (then bufA needs no clearing)
 	int batch = 0;                 // codewords of the call (r.B may shrink to the active list; the OSD sums cover every codeword)
@@ -947,7 +907,6 @@ static hipError_t mark(IterCtx &c, int t, hipStream_t st)
 static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t st, bool count)
 {
 	nbl_decoder *d = c.d;
-	const nbl_params &p = d->prm;
 	for (int it = it_lo; it <= it_hi; it++) {
 		c.r.iter = it;
 		if (d->layered) {
@@ -959,30 +918,22 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			HIP_TRY(d, mark(c, 1, st));
 			// (T-EMS: each check also damps its inputs against the v2c buffer and updates it in place; init_kernel has set v2c = L_ch)
 			for (int l = 0; l < d->n_layers; l++) {
-				if (p.method == NBL_METHOD_TEMS) HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
+				if (c.plan.cn == NBL_CN_TEMS_LAYERED) HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
 				else HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
 			}
 			HIP_TRY(d, mark(c, 2, st));
 			if (count) { d->launches[0]++; d->launches[1]++; d->launches[2] += d->n_layers; }
 			continue;
 		}
-		if (c.fused) {
+		if (c.plan.fused) {
 			// one launch = variable-node pass + check-node pass; c2v ping-pongs between the two buffers
 			NblWork wf = d->w;
 			wf.c2v_prev = (it == 1 && c.zeros) ? c.zeros : (it & 1) ? c.bufA : c.bufB;
 			wf.c2v_prev_shared = (it == 1 && c.zeros) ? 1 : 0;
 			wf.c2v = (it & 1) ? c.bufB : c.bufA;
 			wf.store_v2c = d->record_state ? 1 : 0;
-			if (small_shape(d)) {
-				if (p.method == NBL_METHOD_EMS) HIP_TRY(d, nbl_launch_cn_ems_small(d->g, wf, c.r, true, st));
-				else if (p.method == NBL_METHOD_TEMS) HIP_TRY(d, nbl_launch_cn_tems_small(d->g, wf, c.r, true, st));
-				else HIP_TRY(d, nbl_launch_cn_bp_small(d->g, wf, c.r, true, st));
-			} else if (p.method == NBL_METHOD_EMS && d->g.q == 64) HIP_TRY(d, nbl_launch_cn_ems64(d->g, wf, c.r, true, st));
-			else if (p.method == NBL_METHOD_EMS) HIP_TRY(d, nbl_launch_cn_ems256(d->g, wf, c.r, true, st));
-			else if (p.method == NBL_METHOD_TEMS && d->g.q == 64) HIP_TRY(d, nbl_launch_cn_tems64(d->g, wf, c.r, true, st));
-			else if (p.method == NBL_METHOD_TEMS) HIP_TRY(d, nbl_launch_cn_tems256(d->g, wf, c.r, true, st));
-			else if (d->g.q == 64) HIP_TRY(d, nbl_launch_cn_bp64(d->g, wf, c.r, true, st));
-			else HIP_TRY(d, nbl_launch_cn_bp256(d->g, wf, c.r, true, st));
+			const nbl_status s = launch_cn(d, c.plan.cn, wf, c.r, true, st);
+			if (s) return s;
 			HIP_TRY(d, mark(c, 2, st));
 			if (d->osd_acc) {
 				HIP_TRY(d, nbl_launch_osd_acc(d->w.post, d->osd_S, c.batch, d->g.N, d->g.p, d->g.q, d->osd_factor, it == 1, st));
@@ -1004,7 +955,7 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 		if (count) { d->launches[0]++; d->launches[1]++; }
 		// (the reference leaves the loop after the syndrome check of the last iteration it runs; the check-node pass of a
 		// window's last iteration is only needed if another window follows -- it is cheap to keep the windows uniform)
-		nbl_status s = launch_cn(d, c.r, st);
+		const nbl_status s = launch_cn(d, c.plan.cn, d->w, c.r, false, st);
 		if (s) return s;
 		HIP_TRY(d, mark(c, 2, st));
 		if (count) d->launches[2]++;
@@ -1037,7 +988,7 @@ static nbl_status run_window(IterCtx &c, int widx, int it_lo, int it_hi, hipStre
 			HIP_TRY(d, hipGraphLaunch(d->gexec[widx], st));
 			const int n = it_hi - it_lo + 1;
 			d->launches[1] += n; d->launches[2] += d->layered ? (long long)n * d->n_layers : n;
-			if (!c.fused) d->launches[0] += n;
+			if (!c.plan.fused) d->launches[0] += n;
 			return NBL_OK;
 		}
 	}
@@ -1060,19 +1011,19 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 	r.damp_old = (p.method == NBL_METHOD_BP) ? 0.5 : 0.25;  // NBLDPC.cpp:739 / :1046 / :1262
 	r.damp_new = (p.method == NBL_METHOD_BP) ? 0.5 : 0.75;
 	d->launches[0] = d->launches[1] = d->launches[2] = 0;
-	c.fused = fused_shape(d) && d->force_generic == 0 && d->c2v_alt;
+	c.plan = plan_of(d); // (ensure_workspace has made c2v_alt and c2v_zero for every fusable shape)
 	c.bufA = d->w.c2v;
 	c.bufB = d->c2v_alt;
-	c.zeros = c.fused ? d->c2v_zero : nullptr;
+	c.zeros = c.plan.fused ? d->c2v_zero : nullptr;
 	// the captured graphs hold buffer addresses and the batch size: any change drops them
-	const nbl_decoder::GraphKey key = {d_Lin, d->w.Lch, d->w.v2c, d->w.c2v, d->c2v_alt, d->w.post, d->osd_S, B, d->record_state ? 1 : 0, d->force_generic, c.fused ? 1 : 0};
+	const nbl_decoder::GraphKey key = {d_Lin, d->w.Lch, d->w.v2c, d->w.c2v, d->c2v_alt, d->w.post, d->osd_S, B, d->record_state ? 1 : 0, d->force_generic, c.plan.fused ? 1 : 0};
 	c.batch = B;
 	if (memcmp(&key, &d->gkey, sizeof key) != 0) { drop_graphs(d); d->gkey = key; }
 	HIP_TRY(d, mark(c, 3, st));
 	HIP_TRY(d, nbl_launch_init(d_Lin, d->g, d->w, B, (c.damp ? 1 : 0) | (c.zeros ? 2 : 0), st)); // bit 1: c2v is not cleared
 	HIP_TRY(d, mark(c, 3, st));
 	d->last_c2v = c.zeros ? c.zeros : c.bufA;
-	d->last_fused = c.fused;
+	d->last_fused = c.plan.fused;
 	// windows: fixed iterations or no polling -> one window; early exit -> `poll_every` iterations, then ask the device
 	const bool polling = !p.fixed_iters && p.poll_every > 0;
 	const int wlen = polling ? p.poll_every : (p.max_iter > 0 ? p.max_iter : 1);
@@ -1118,7 +1069,7 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 		HIP_TRY(d, mark(c, 3, st));
 	}
 	if (polling) HIP_TRY(d, hipStreamSynchronize(st));
-	if (c.fused && last_it > 0) d->last_c2v = (last_it & 1) ? c.bufB : c.bufA;
+	if (c.plan.fused && last_it > 0) d->last_c2v = (last_it & 1) ? c.bufB : c.bufA;
 	if (d->profiling && c.nev > 0) {
 		HIP_TRY(d, hipEventSynchronize(d->pev[c.nev - 1]));
 		d->ms[0] = d->ms[1] = d->ms[2] = d->ms[3] = 0;

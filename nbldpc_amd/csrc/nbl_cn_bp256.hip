@@ -450,7 +450,7 @@ __global__ __launch_bounds__(64, 3) void cn_bp_q256_dc4_kernel(NblGraphDev g, Nb
 
 } // namespace
 
-bool nbl_bp256_applicable(const NblGraphDev &g, bool all_dc4) { return g.q == 256 && all_dc4; }
+bool nbl_bp256_applicable(const NblShape &s) { return s.q == 256 && s.all_dc4; }
 
 hipError_t nbl_launch_cn_bp256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
 {

@@ -426,7 +426,7 @@ __global__ __launch_bounds__(64) void cn_bp_q64_dc4_kernel(NblGraphDev g, NblWor
 
 } // namespace
 
-bool nbl_bp64_applicable(const NblGraphDev &g, bool all_dc4) { return g.q == 64 && all_dc4; }
+bool nbl_bp64_applicable(const NblShape &s) { return s.q == 64 && s.all_dc4; }
 
 hipError_t nbl_launch_cn_bp64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
 {

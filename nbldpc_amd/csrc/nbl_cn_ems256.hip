@@ -921,9 +921,9 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 #undef TOFF
 }
 
-bool nbl_ems256_applicable(const NblGraphDev &g, bool all_dc4, int nm, int nc)
+bool nbl_ems256_applicable(const NblShape &s, int nm, int nc)
 {
-	return g.q == 256 && all_dc4 && nc >= 1 && nm >= 1 && nm <= 64 && g.ems_toff != nullptr; // (fused: g.dv2_row too, see fused_shape)
+	return s.has_ems_toff() && nc >= 1 && nm >= 1 && nm <= 64; // (reads g.ems_toff; fused: g.dv2_row too, NblShape::has_dv2_row)
 }
 
 size_t nbl_ems256_lds_bytes(int nm) { return 3 * Q * 8 + (size_t)4 * (nm <= 8 ? 8 : nm <= 16 ? 16 : nm <= 32 ? 32 : 64) * 16; }

@@ -382,16 +382,16 @@ __global__ __launch_bounds__(64) void cn_ems_q64_kernel(NblGraphDev g, NblWork w
 } // namespace
 
 // GF(64), check degrees 3..8, at most four deviation-count layers, the four checks of a wave within 64 KB of LDS
-bool nbl_ems64_applicable(const NblGraphDev &g, int min_dc, int nm, int nc)
+bool nbl_ems64_applicable(const NblShape &s, int nm, int nc)
 {
-	if (g.q != 64 || min_dc < 3 || g.maxdc > NBL_MAXDC) return false;
-	const int layers = nbl_ems_layers(g, nc);
-	return layers <= 4 && group_bytes(g.maxdc, nm, layers) * 4 <= 64 * 1024;
+	if (s.q != 64 || s.min_dc < 3 || s.maxdc > NBL_MAXDC) return false;
+	const int layers = nbl_ems_layers(s.maxdc, nc);
+	return layers <= 4 && group_bytes(s.maxdc, nm, layers) * 4 <= 64 * 1024;
 }
 
 hipError_t nbl_launch_cn_ems64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
 {
-	const int layers = nbl_ems_layers(g, r.nc);
+	const int layers = nbl_ems_layers(g.maxdc, r.nc);
 	const size_t lds = group_bytes(g.maxdc, r.nm, layers) * 4;
 	dim3 grid(nbl_xcd_grid(r.B, (g.M + 3) >> 2)), block(64);
 	if (fused) cn_ems_q64_kernel<true><<<grid, block, lds, st>>>(g, w, r, layers);

@@ -109,8 +109,8 @@ hipError_t nbl_launch_vn_decide(const NblGraphDev &g, const NblWork &w, const Nb
 
 hipError_t nbl_launch_cn_ems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st)
 {
-	const int layers = nbl_ems_layers(g, r.nc);
-	const size_t lds = nbl_ems_lds_bytes(g, r.nm, layers);
+	const int layers = nbl_ems_layers(g.maxdc, r.nc);
+	const size_t lds = nbl_ems_lds_bytes(g.q, g.maxdc, r.nm, r.nc);
 	const long long blocks = (long long)r.B * count;
 	if (count < 1 || offset < 0 || offset + count > g.M || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
 	if (lds > 160 * 1024) return hipErrorInvalidValue; // (nbl_create_layered refuses such shapes)

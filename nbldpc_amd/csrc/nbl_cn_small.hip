@@ -694,7 +694,7 @@ template <int Q> struct SmallLaunch {
 	}
 	static hipError_t ems(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
 	{
-		const int layers = nbl_ems_layers(g, r.nc);
+		const int layers = nbl_ems_layers(g.maxdc, r.nc);
 		const size_t lds = ems_small_group_bytes(Q, g.maxdc, r.nm, layers) * G;
 		if (r.nm == 8 && Q >= 8) {
 			if (fused) cn_ems_small_kernel<Q, true, (Q >= 8 ? 8 : 0)><<<grid(g, r), dim3(64), lds, st>>>(g, w, r, layers);
@@ -716,18 +716,18 @@ template <int Q> struct SmallLaunch {
 
 } // namespace
 
-// (fused launches additionally need g.c_nbr: variable degrees <= 3 -- nbl_api.cpp)
+// (fused launches additionally need g.c_nbr, NblShape::has_c_nbr: variable degrees 2 and 3 -- nbl_plan.cpp)
 // q <= 64, every check of degree >= 3 (the log-QSPA schedule below needs a middle edge), the LDS of a wave's 64 / q checks
 // within the 64 KB a launch gets without opting in; T-EMS: nc <= 3 and a path code of p * maxdc <= 32 bits as in the general kernel
-bool nbl_small_applicable(const NblGraphDev &g, int method, int min_dc, int nm, int nc)
+bool nbl_small_applicable(const NblShape &s, int method, int nm, int nc)
 {
 	// (q = 64, one check per wave: measured on the BDS code, B = 4096 -- log-QSPA gains 23 % from the fused iteration, EMS loses
 	//  11 % to the 64-step ranking loop; T-EMS not measured on an irregular GF(64) code, so it stays with the general kernel too)
-	if (g.q > (method == 1 ? 64 : 32) || g.q < 4 || min_dc < 3 || g.maxdc > NBL_MAXDC) return false;
-	const int G = 64 / g.q;
-	if (method == 2) return nbl_ems_layers(g, nc) <= 4 && ems_small_group_bytes(g.q, g.maxdc, nm, nbl_ems_layers(g, nc)) * G <= 64 * 1024;
-	if (method == 4) return nc <= 3 && g.p * g.maxdc <= 32 && tems_small_group_bytes(g.q, g.maxdc) * G <= 64 * 1024;
-	if (method == 1) return bp_small_group_bytes(g.q, g.maxdc) * G <= 64 * 1024;
+	if (s.q > (method == 1 ? 64 : 32) || s.q < 4 || s.min_dc < 3 || s.maxdc > NBL_MAXDC) return false;
+	const int G = 64 / s.q;
+	if (method == 2) return nbl_ems_layers(s.maxdc, nc) <= 4 && ems_small_group_bytes(s.q, s.maxdc, nm, nbl_ems_layers(s.maxdc, nc)) * G <= 64 * 1024;
+	if (method == 4) return nc <= 3 && s.p * s.maxdc <= 32 && tems_small_group_bytes(s.q, s.maxdc) * G <= 64 * 1024;
+	if (method == 1) return bp_small_group_bytes(s.q, s.maxdc) * G <= 64 * 1024;
 	return false;
 }
 

@@ -362,9 +362,9 @@ __global__ __launch_bounds__(64, 4) void cn_tems_q256_dc4_kernel(NblGraphDev g, 
 
 } // namespace
 
-bool nbl_tems256_applicable(const NblGraphDev &g, bool all_dc4, int nr, int nc)
+bool nbl_tems256_applicable(const NblShape &s, int nr, int nc)
 {
-	return g.q == 256 && all_dc4 && nc >= 1 && nc <= 3 && nr >= 1 && nr <= 4;
+	return s.q == 256 && s.all_dc4 && nc >= 1 && nc <= 3 && nr >= 1 && nr <= 4;
 }
 
 hipError_t nbl_launch_cn_tems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)

@@ -306,9 +306,9 @@ __global__ __launch_bounds__(64) void cn_tems_q64_dc4_kernel(NblGraphDev g, NblW
 
 } // namespace
 
-bool nbl_tems64_applicable(const NblGraphDev &g, bool all_dc4, int nr, int nc)
+bool nbl_tems64_applicable(const NblShape &s, int nr, int nc)
 {
-	return g.q == 64 && all_dc4 && nc >= 1 && nc <= 3 && nr >= 1 && nr <= 4;
+	return s.q == 64 && s.all_dc4 && nc >= 1 && nc <= 3 && nr >= 1 && nr <= 4;
 }
 
 hipError_t nbl_launch_cn_tems64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)

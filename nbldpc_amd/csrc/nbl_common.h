@@ -16,6 +16,16 @@
 #define NBL_MAXDC 8   // largest check degree supported by the kernels (reference codes: 4 and 5)
 #define NBL_MAXDV 8
 
+// What the choice of a check-node kernel depends on (nbl_plan.cpp): filled once, by nbl_shape(), from the degree arrays of
+// nbl_code_desc.  The three predicates say which of NblGraphDev's optional tables nbl_create uploads.
+struct NblShape {
+	int q, p, maxdc, min_dc, maxdv, mindv;
+	bool all_dc4, all_dv2; // every check of degree 4; every variable of degree 2
+	bool has_ems_toff() const { return q == 256 && all_dc4; }
+	bool has_dv2_row() const { return all_dc4 && all_dv2; }
+	bool has_c_nbr() const { return q <= 64 && maxdv <= 3 && mindv >= 2; } // (variable degrees 2 and 3 only)
+};
+
 struct NblGraphDev {
 	int N, M, E, q, p, poly, maxdc, maxdv;
 	const int *voff;    // [N+1] variable-major edge offsets
@@ -26,11 +36,11 @@ struct NblGraphDev {
 	const int *c_h;     // [E] check-major edge coefficient
 	const int *c_hinv;  // [E] inverse coefficient
 	const uint8_t *mul; // [q*q] GF multiplication table (syndrome kernel)
-	const int *c_nbr;   // [E][4] q <= 64, variable degrees 2 and 3 only (else NULL): for check-major edge e of variable n the c2v slots of
+	const int *c_nbr;   // [E][4] NblShape::has_c_nbr only (else NULL): for check-major edge e of variable n the c2v slots of
 	                    // n's edges in order (third = -1 at degree 2) and, in [3], 1 if e is n's first edge (nbl_cn_small.hip, fused)
-	const unsigned long long *ems_toff; // [E][64] GF(256), all checks of degree 4 only (else NULL): for check-major edge e and lane l the
+	const unsigned long long *ems_toff; // [E][64] NblShape::has_ems_toff only (else NULL): for check-major edge e and lane l the
 	                    // byte offsets 8 * (h_e * a) of a = 2l, 2l+1, 128+2l, 129+2l, 16 bits each (nbl_cn_ems256.hip)
-	const int *dv2_row; // [M][16] every check of degree 4 and every variable of degree 2 only (else NULL): all a fused iteration needs
+	const int *dv2_row; // [M][16] NblShape::has_dv2_row only (else NULL): all a fused iteration needs
 	                    // to address the inputs of check m, in ONE 64-byte row: [0..3] variable of edge j, [4..7] c2v slot of that
 	                    // variable's first edge, [8..11] of its second edge, [12..15] variable-major position of edge j, bit 31 set
 	                    // when edge j IS the variable's first edge (one scalar load instead of a chain of four dependent ones)

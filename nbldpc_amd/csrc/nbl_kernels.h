@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "nbl_common.h"
+#include "nbl_plan.h" // the nbl_*_applicable predicates, defined beside their kernels
 
 hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblWork &w, int B, int write_v2c, hipStream_t st);
 hipError_t nbl_launch_demod(const double *d_rx, int L, double sigma, int mod_order, const double *d_cons, const int *d_src,
@@ -14,8 +15,9 @@ hipError_t nbl_launch_syn(const NblGraphDev &g, const NblWork &w, const NblRun &
 hipError_t nbl_launch_compact(const uint8_t *done, int B, int *active, int *n_act, hipStream_t st);
 hipError_t nbl_launch_cn_ems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_unpad(const double *src, double *dst, const int *map, int rows, int q, hipStream_t st);
-size_t nbl_ems_lds_bytes(const NblGraphDev &g, int nm, int layers);
-int nbl_ems_layers(const NblGraphDev &g, int nc);
+// general EMS kernel: deviation-count layers, and the bytes of LDS of one check (pure arithmetic: nbl_create refuses above 160 KB)
+int nbl_ems_layers(int maxdc, int nc);
+size_t nbl_ems_lds_bytes(int q, int maxdc, int nm, int nc);
 
 // layered schedule for EMS (nbl_cn_layered.hip): decision + posterior without the v2c write, and the checks of one layer
 // (chk[offset] .. chk[offset + count - 1]), inputs formed from L_ch and the in-place c2v
@@ -29,7 +31,6 @@ size_t nbl_tems_layered_lds_bytes(int q, int maxdc, int nc);
 hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
 // specialised EMS check node (nbl_cn_ems256.hip)
-bool nbl_ems256_applicable(const NblGraphDev &g, bool all_dc4, int nm, int nc);
 size_t nbl_ems256_lds_bytes(int nm);
 hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
@@ -38,18 +39,15 @@ hipError_t nbl_launch_cn_tems(const NblGraphDev &g, const NblWork &w, const NblR
 bool nbl_tems_use_fast(int nc); // the fast programme (nc <= 3) unless NBL_TEMS_GENERIC is set (A/B runs)
 hipError_t nbl_launch_cn_bp(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 
-// small fields (q <= 32), 64 / q checks per wave (nbl_cn_small.hip); method as in include/nbldpc.h (1 BP, 2 EMS, 4 T-EMS)
-bool nbl_small_applicable(const NblGraphDev &g, int method, int min_dc, int nm, int nc);
+// small fields (q <= 32; log-QSPA also q = 64), 64 / q checks per wave (nbl_cn_small.hip); method as in include/nbldpc.h (1 BP, 2 EMS, 4 T-EMS)
 hipError_t nbl_launch_cn_ems_small(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 hipError_t nbl_launch_cn_tems_small(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 hipError_t nbl_launch_cn_bp_small(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
 // T-EMS check node for GF(64), check degree 4 (nbl_cn_tems64.hip)
-bool nbl_tems64_applicable(const NblGraphDev &g, bool all_dc4, int nr, int nc);
 hipError_t nbl_launch_cn_tems64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
 // T-EMS check node for GF(256), check degree 4 (nbl_cn_tems256.hip)
-bool nbl_tems256_applicable(const NblGraphDev &g, bool all_dc4, int nr, int nc);
 hipError_t nbl_launch_cn_tems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
 // basic-set T-EMS check node, any q = 4 .. 256, check degree <= 8, 1 <= nm <= min(q - 1, 16) (nbl_cn_bstems.hip)
@@ -58,15 +56,12 @@ size_t nbl_bstems_lds_bytes(const NblGraphDev &g);
 hipError_t nbl_launch_cn_bstems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 
 // log-QSPA check node for GF(256), check degree 4 (nbl_cn_bp256.hip)
-bool nbl_bp256_applicable(const NblGraphDev &g, bool all_dc4);
 hipError_t nbl_launch_cn_bp256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
 // EMS check node for GF(64): four checks per wave, four symbols per lane (nbl_cn_ems64.hip)
-bool nbl_ems64_applicable(const NblGraphDev &g, int min_dc, int nm, int nc);
 hipError_t nbl_launch_cn_ems64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
 // log-QSPA check node for GF(64), check degree 4: four checks per wave, four symbols per lane (nbl_cn_bp64.hip)
-bool nbl_bp64_applicable(const NblGraphDev &g, bool all_dc4);
 hipError_t nbl_launch_cn_bp64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
 // AWGN channel + CRand on the device (nbl_noise.hip)

@@ -388,21 +388,21 @@ hipError_t nbl_launch_syn(const NblGraphDev &g, const NblWork &w, const NblRun &
 	return hipGetLastError();
 }
 
-size_t nbl_ems_lds_bytes(const NblGraphDev &g, int nm, int layers)
+int nbl_ems_layers(int maxdc, int nc)
 {
-	size_t doubles = (size_t)g.maxdc * g.q + (2 * (size_t)layers + 1) * g.q + (size_t)g.maxdc * nm;
-	return doubles * 8 + (size_t)g.maxdc * nm * 4 + 16;
+	return (nc >= maxdc - 1) ? 1 : nc + 1;
 }
 
-int nbl_ems_layers(const NblGraphDev &g, int nc)
+size_t nbl_ems_lds_bytes(int q, int maxdc, int nm, int nc)
 {
-	return (nc >= g.maxdc - 1) ? 1 : nc + 1;
+	size_t doubles = (size_t)maxdc * q + (2 * (size_t)nbl_ems_layers(maxdc, nc) + 1) * q + (size_t)maxdc * nm;
+	return doubles * 8 + (size_t)maxdc * nm * 4 + 16;
 }
 
 hipError_t nbl_launch_cn_ems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st)
 {
-	const int layers = nbl_ems_layers(g, r.nc);
-	const size_t lds = nbl_ems_lds_bytes(g, r.nm, layers);
+	const int layers = nbl_ems_layers(g.maxdc, r.nc);
+	const size_t lds = nbl_ems_lds_bytes(g.q, g.maxdc, r.nm, r.nc);
 	dim3 grid((unsigned)((long long)r.B * g.M)), block(64);
 	if (lds > 160 * 1024) return hipErrorInvalidValue; // (nbl_create refuses such shapes)
 	NBL_DISPATCH_Q(g.q, {

@@ -1,0 +1,82 @@
+// nbldpc_amd/csrc/nbl_plan.cpp -- which check-node kernel runs, whether the iteration is fused, which buffers must exist.
+//
+// Precedence of the specialised kernels (the first that can run the shape; the general kernel otherwise):
+//   EMS       256, small, 64
+//   T-EMS     64, 256, small
+//   log-QSPA  256, 64, small     (so a (.,4)-regular GF(64) code with variables of degree 3 runs BP-64 unfused, although BP-small
+//                                 could run fused there: changing that is a performance decision, and needs a measurement)
+// The fused iteration is the same kernel with the variable-node pass inside; it needs the per-edge neighbour rows the kernel reads.
+#include "nbl_plan.h"
+
+NblShape nbl_shape(const nbl_code_desc *code)
+{
+	NblShape s{};
+	s.q = code->q;
+	while ((1 << s.p) < s.q) s.p++;
+	s.min_dc = code->chk_deg[0];
+	s.mindv = code->var_deg[0];
+	for (int m = 0; m < code->M; m++) {
+		const int dc = code->chk_deg[m];
+		s.maxdc = dc > s.maxdc ? dc : s.maxdc;
+		s.min_dc = dc < s.min_dc ? dc : s.min_dc;
+	}
+	for (int n = 0; n < code->N; n++) {
+		const int dv = code->var_deg[n];
+		s.maxdv = dv > s.maxdv ? dv : s.maxdv;
+		s.mindv = dv < s.mindv ? dv : s.mindv;
+	}
+	s.all_dc4 = s.min_dc == 4 && s.maxdc == 4;
+	s.all_dv2 = s.mindv == 2 && s.maxdv == 2;
+	return s;
+}
+
+static const char *const cn_names[NBL_CN_COUNT] = {
+	"ems256", "ems_small", "ems64", "ems", "tems64", "tems256", "tems_small", "tems", "bp256", "bp64", "bp_small", "bp",
+	"bstems", "ems_layered", "tems_layered", "none"};
+
+const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
+
+NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &, bool layered, int force_generic, bool record_state,
+                 bool small_on)
+{
+	NblPlan pl{NBL_CN_NONE, false, false, true};
+	if (layered) { // one c2v buffer updated in place: never fused; T-EMS keeps the v2c its damping reads
+		pl.cn = prm.method == NBL_METHOD_TEMS ? NBL_CN_TEMS_LAYERED : NBL_CN_EMS_LAYERED;
+		pl.want_v2c = prm.method == NBL_METHOD_TEMS;
+		return pl;
+	}
+	NblCn general = NBL_CN_NONE, special = NBL_CN_NONE;
+	switch (prm.method) {
+	case NBL_METHOD_EMS:
+		general = NBL_CN_EMS;
+		if (nbl_ems256_applicable(s, prm.ems_nm, prm.ems_nc)) special = NBL_CN_EMS256;
+		else if (small_on && nbl_small_applicable(s, NBL_METHOD_EMS, prm.ems_nm, prm.ems_nc)) special = NBL_CN_EMS_SMALL;
+		else if (small_on && nbl_ems64_applicable(s, prm.ems_nm, prm.ems_nc)) special = NBL_CN_EMS64;
+		break;
+	case NBL_METHOD_TEMS:
+		general = NBL_CN_TEMS;
+		if (nbl_tems64_applicable(s, prm.tems_nr, prm.tems_nc)) special = NBL_CN_TEMS64;
+		else if (nbl_tems256_applicable(s, prm.tems_nr, prm.tems_nc)) special = NBL_CN_TEMS256;
+		else if (small_on && nbl_small_applicable(s, NBL_METHOD_TEMS, 0, prm.tems_nc)) special = NBL_CN_TEMS_SMALL;
+		break;
+	case NBL_METHOD_BP:
+		general = NBL_CN_BP;
+		if (nbl_bp256_applicable(s)) special = NBL_CN_BP256;
+		else if (nbl_bp64_applicable(s)) special = NBL_CN_BP64;
+		else if (small_on && nbl_small_applicable(s, NBL_METHOD_BP, 0, 0)) special = NBL_CN_BP_SMALL;
+		break;
+	case NBL_METHOD_BS_TEMS: general = NBL_CN_BSTEMS; break; // (its launcher picks the field's instantiation)
+	default: break;                                          // method 6: no iteration
+	}
+	switch (special) {
+	case NBL_CN_NONE: break;
+	case NBL_CN_EMS_SMALL: case NBL_CN_TEMS_SMALL: case NBL_CN_BP_SMALL: case NBL_CN_EMS64: pl.fusable = s.has_c_nbr(); break;
+	default: pl.fusable = s.has_dv2_row(); break;
+	}
+	pl.cn = (special == NBL_CN_NONE || force_generic == 1) ? general : special;
+	pl.fused = pl.fusable && force_generic == 0;
+	// v2c only exists in HBM when something reads it: the unfused path, or state read-back
+	// (damped methods always keep it: the damping reads the previous iteration's v2c)
+	pl.want_v2c = prm.method != NBL_METHOD_EMS || !pl.fusable || record_state || force_generic != 0;
+	return pl;
+}

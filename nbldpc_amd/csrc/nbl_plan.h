@@ -1,0 +1,38 @@
+// nbldpc_amd/csrc/nbl_plan.h -- the one place where a shape meets a check-node kernel (nbl_plan.cpp; pure host code, no HIP)
+#pragma once
+#include "../../include/nbldpc.h"
+#include "nbl_common.h"
+
+enum NblCn {
+	NBL_CN_EMS256, NBL_CN_EMS_SMALL, NBL_CN_EMS64, NBL_CN_EMS,
+	NBL_CN_TEMS64, NBL_CN_TEMS256, NBL_CN_TEMS_SMALL, NBL_CN_TEMS,
+	NBL_CN_BP256, NBL_CN_BP64, NBL_CN_BP_SMALL, NBL_CN_BP,
+	NBL_CN_BSTEMS, NBL_CN_EMS_LAYERED, NBL_CN_TEMS_LAYERED,
+	NBL_CN_NONE, // method 6: no iteration
+	NBL_CN_COUNT
+};
+
+struct NblPlan {
+	NblCn cn;      // the check-node kernel of every iteration
+	bool fusable;  // the shape has a fused iteration (variable-node pass inside cn): c2v_alt and c2v_zero exist
+	bool fused;    // this decode runs it
+	bool want_v2c; // v2c exists in HBM: something reads it (the unfused path, the damped methods, state read-back)
+};
+
+NblShape nbl_shape(const nbl_code_desc *code);
+// force_generic: nbl_debug_force_generic's value (1 = the general kernel, 2 = the specialised one, neither fused);
+// small_on: the kernels NBL_NO_SMALL switches off (EMS-small, T-EMS-small, BP-small, EMS-64) may be chosen
+NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
+                 bool small_on);
+const char *nbl_cn_name(NblCn cn);
+
+// What each specialised kernel can run, beside the kernel (its LDS arithmetic lives there); nbl_plan is the only caller.
+// method: NBL_METHOD_* of include/nbldpc.h.  Unfused: any variable degrees.  Fused: NblShape::has_c_nbr for the small-field and the
+// EMS-64 kernel, NblShape::has_dv2_row for the others.
+bool nbl_ems256_applicable(const NblShape &s, int nm, int nc);             // nbl_cn_ems256.hip
+bool nbl_small_applicable(const NblShape &s, int method, int nm, int nc);  // nbl_cn_small.hip: q <= 32, log-QSPA also q = 64
+bool nbl_ems64_applicable(const NblShape &s, int nm, int nc);              // nbl_cn_ems64.hip
+bool nbl_tems64_applicable(const NblShape &s, int nr, int nc);             // nbl_cn_tems64.hip
+bool nbl_tems256_applicable(const NblShape &s, int nr, int nc);            // nbl_cn_tems256.hip
+bool nbl_bp256_applicable(const NblShape &s);                              // nbl_cn_bp256.hip
+bool nbl_bp64_applicable(const NblShape &s);                               // nbl_cn_bp64.hip

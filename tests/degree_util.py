@@ -127,3 +127,19 @@ def write_spec_code_file(spec, path):
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
     return path
+
+
+def ring_code(q, M, dc):
+    """A synthetic (2, dc)-regular graph (dc even): M checks, N = M dc / 2 variables; variable n joins checks n % M and
+    (n % M + 1 + n // M) % M -- two different checks, every check gets dc / 2 variables from each rule."""
+    assert dc % 2 == 0 and M > dc // 2
+    N = M * dc // 2
+    chk_rows = [[] for _ in range(M)]
+    var_rows = [[] for _ in range(N)]
+    for n in range(N):
+        for m in (n % M, (n % M + 1 + n // M) % M):
+            h = 1 + (7 * n + 3 * m) % (q - 1)
+            var_rows[n].append((m + 1, h))
+            chk_rows[m].append((n + 1, h))
+    import nbldpc_amd as nb
+    return nb.Code(spec=dict(N=N, M=M, q=q, var_rows=var_rows, chk_rows=chk_rows))

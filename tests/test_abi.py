@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import nbldpc_amd as nb
+from degree_util import ring_code as _ring_code
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -81,21 +82,6 @@ def test_no_device_means_error_not_fallback():
     with pytest.raises(nb.NblError) as e:
         _create(code, method=nb.METHOD_EMS, max_iter=5, ems_nm=8)
     assert e.value.status == -3 and "no CPU decode path" in str(e.value)
-
-
-def _ring_code(q, M, dc):
-    """A synthetic (2, dc)-regular graph (dc even): M checks, N = M dc / 2 variables; variable n joins checks n % M and
-    (n % M + 1 + n // M) % M -- two different checks, every check gets dc / 2 variables from each rule."""
-    assert dc % 2 == 0 and M > dc // 2
-    N = M * dc // 2
-    chk_rows = [[] for _ in range(M)]
-    var_rows = [[] for _ in range(N)]
-    for n in range(N):
-        for m in (n % M, (n % M + 1 + n // M) % M):
-            h = 1 + (7 * n + 3 * m) % (q - 1)
-            var_rows[n].append((m + 1, h))
-            chk_rows[m].append((n + 1, h))
-    return nb.Code(spec=dict(N=N, M=M, q=q, var_rows=var_rows, chk_rows=chk_rows))
 
 
 def test_create_refuses_shapes_the_kernels_cannot_run():
@@ -201,7 +187,7 @@ def test_create_refuses_tems_path_codes_above_32_bits():
 
 
 def test_create_refuses_ems_shapes_above_160_kb_of_lds():
-    """General EMS kernel, bytes of LDS for one check (nbl_api.cpp): (maxdc q + (2 layers + 1) q + maxdc nm) 8 + maxdc nm 4 + 16
+    """General EMS kernel, bytes of LDS for one check (nbl_ems_lds_bytes, nbl_kernels.hip): (maxdc q + (2 layers + 1) q + maxdc nm) 8 + maxdc nm 4 + 16
     with layers = nc + 1 below nc = maxdc - 1, else 1.  Inside the envelope the other checks of nbl_create leave (q <= 256,
     degrees <= 8, nm <= q) the largest value is 71,696 B (GF(256), check degree 8, nm = 256, nc = 6), so NO accepted shape
     reaches the 160 KB refusal: there is no 'just above' shape to create, and the one nearest to the bound must be accepted.

@@ -12,7 +12,8 @@ import pytest
 import nbldpc_amd as nb
 from conftest import load_golden, decoder_kwargs
 from bstems_util import CANONICAL as BS_CANONICAL, LITERAL as BS_LITERAL, bs_kwargs, build_checker, run_checker
-from degree_util import PROFILES, QS, TEMS_REFUSED, degree_code, profile_code, spec_edges
+from degree_util import PROFILES, QS, TEMS_REFUSED, degree_code, profile_code, ring_code, spec_edges
+from nbldpc_amd.binding import debug_plan
 from test_gpu_parity import LLR_TOL, _bpsk_llr_zero, _force_generic
 
 pytestmark = pytest.mark.gpu
@@ -273,27 +274,38 @@ def test_early_exit_fixed_iterations_and_active_list_on_high_degrees(oracle, che
         dec.close()
 
 
+RING256 = {"ems": (nb.METHOD_EMS, dict(ems_nm=32, ems_nc=3)), "tems": (nb.METHOD_TEMS, dict(tems_nr=2, tems_nc=3)), "bp": (nb.METHOD_BP, dict())}
+
+
 @pytest.mark.parametrize("method", ["ems", "tems", "bp"])
-@pytest.mark.parametrize("q", [16, 64])
+@pytest.mark.parametrize("q", [16, 64, 256])
 def test_which_iteration_ran(q, method):
     """nbl_last_timing's launch counters: the fused iteration makes no variable-node launch.  dc78 (variables of degree 2 / 3) runs
     fused under the default kernel choice; dv4edge (ONE variable of degree 4) and dv48 take the separate variable-node launch,
-    as does every code under variants 1 and 2.  (This separates fused from unfused only; that the small-field and the general
-    check-node kernels agree is what the three variants against the oracle show.)"""
-    for profile, fused in (("dc78", True), ("dv4edge", False), ("dv48", False)):
-        if method == "tems" and profile == "dc78" and q == 64:
-            continue  # (refused: 6 * 8 bits of path code)
-        code, _, _ = profile_code(profile, q, method)
-        meth, kw, _ = method_runs(method, q)[0]
+    as does every code under variants 1 and 2.  GF(256): an 8-check (2,4) ring, fused under the EMS-256, T-EMS-256 and BP-256
+    kernels.  nbl_debug_plan reports the same `fused` for every cell.  (This separates fused from unfused only; WHICH kernel
+    serves a shape is pinned by tests/test_plan.py, and that the kernels agree by the three variants against the oracle.)"""
+    if q == 256:
+        code = ring_code(256, 8, 4)
+        cells = [("ring4", True, code) + RING256[method]]
+    else:
+        cells = []
+        for profile, fused in (("dc78", True), ("dv4edge", False), ("dv48", False)):
+            if method == "tems" and profile == "dc78" and q == 64:
+                continue  # (refused: 6 * 8 bits of path code)
+            cells.append((profile, fused, profile_code(profile, q, method)[0]) + method_runs(method, q)[0][:2])
+    for tag, fused, code, meth, kw in cells:
         L = np.random.default_rng(q).normal(-1.5, 3.0, (4, code.N, q - 1))
+        plan_kw = {k: v for k, v in kw.items() if not k.endswith(("_factor", "_offset"))}
         for variant in (0, 1, 2):
             dec = nb.Decoder(code, meth, 3, fixed_iters=1, **kw)
             _force_generic(dec, variant)
             dec.decode(L)
             _, (n_vn, n_syn, n_cn) = dec.last_timing()
             dec.close()
-            assert (n_syn, n_cn) == (3, 3), (profile, variant, n_vn, n_syn, n_cn)
-            assert n_vn == (0 if fused and variant == 0 else 3), (profile, variant, n_vn)
+            assert (n_syn, n_cn) == (3, 3), (tag, variant, n_vn, n_syn, n_cn)
+            assert n_vn == (0 if fused and variant == 0 else 3), (tag, variant, n_vn)
+            assert debug_plan(code, meth, force_generic=variant, **plan_kw)[2] == (fused and variant == 0), (tag, variant)
 
 
 @pytest.mark.parametrize("name", DEG_FIXTURES)
