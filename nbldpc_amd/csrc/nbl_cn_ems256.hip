@@ -694,7 +694,7 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 		ea.t8 ^= sxor << 3;
 		WSYNC();
 		if (fast) { // short lists: the moving operand stops at its last entry
-			for (int it = 0; it < ((cntl[jb] + PER - 1) >> (6 - LOGNM)); it++) {
+			for (int it = 0, nit = __builtin_amdgcn_readfirstlane((cntl[jb] + PER - 1) >> (6 - LOGNM)); it < nit; it++) { // (a scalar bound: a uniform loop)
 				const ListEnt eb = list_at(jb, it * PER + (lane >> LOGNM));
 				__hip_atomic_fetch_max((double *)((char *)dst + (ea.t8 ^ eb.t8)), ea.v + eb.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 			}
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 		ea.v = ea.v + bias;
 		ea.t8 ^= sxor << 3;
 		if (fast) { // short lists: the moving operand stops at its last entry
-			for (int it = 0; it < ((cntl[jb] + PER - 1) >> (6 - LOGNM)); it++) {
+			for (int it = 0, nit = __builtin_amdgcn_readfirstlane((cntl[jb] + PER - 1) >> (6 - LOGNM)); it < nit; it++) {
 				const ListEnt eb = list_at(jb, it * PER + (lane >> LOGNM));
 				__hip_atomic_fetch_max((double *)((char *)dst + (ea.t8 ^ eb.t8)), ea.v + eb.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 			}
@@ -749,7 +749,7 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 	// NP max-plus gather convolutions over ONE list: acc[p][s] = max_k  P_p[s ^ t_k] + v_k, P_p = B0 + p * Q
 	auto gather_conv = [&](int jc, auto np_tag, double (&acc)[decltype(np_tag)::value][4]) {
 		constexpr int NP = decltype(np_tag)::value;
-		constexpr int UN = 4; // entries per trip (twelve 16-byte gathers in flight in the three-way loop)
+		constexpr int UN = 4; // entries per trip (hipcc takes the entries of the three-way loop one after the other: six 16-byte gathers in flight; a software pipeline over them was measured and dropped, DESIGN.md section 4 "Gather loops")
 		const char *Pb = (const char *)B0;
 		// four runs of entries, by bit 0 and bit 7 of the entry's symbol t (both fixed by the slot the entry came from): bit 0 swaps
 		// the values inside a 16-byte slot (SW), bit 7 swaps the lower and the upper half of the vector (HI) -- as compile-time
@@ -811,10 +811,13 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 			}
 			for (; k < k1; k++) { STAMP_COUNT(12); body(entry(k), swapped, upper); }
 		};
-		run(0, nA[jc], std::false_type{}, std::false_type{});
-		run(nA[jc], n0[jc], std::false_type{}, std::true_type{});
-		run(n0[jc], nC[jc], std::true_type{}, std::false_type{});
-		run(nC[jc], cntl[jc], std::true_type{}, std::true_type{});
+		// the run ends are wave-uniform, but they come out of ballots behind wave-uniform branches and end up in VGPRs: handed over as
+		// scalar values the loops below are s_cmp / s_cbranch_scc loops, without the v_cmp + EXEC bookkeeping of a divergent loop
+		const int eA = __builtin_amdgcn_readfirstlane(nA[jc]), e0 = __builtin_amdgcn_readfirstlane(n0[jc]), eC = __builtin_amdgcn_readfirstlane(nC[jc]), eN = __builtin_amdgcn_readfirstlane(cntl[jc]);
+		run(0, eA, std::false_type{}, std::false_type{});
+		run(eA, e0, std::false_type{}, std::true_type{});
+		run(e0, eC, std::true_type{}, std::false_type{});
+		run(eC, eN, std::true_type{}, std::true_type{});
 	};
 	// c2v[a] = shape(S[h_x a] - S[0]) (:899-916): the output goes back to the variable domain through LDS
 	auto emit_stage = [&](int x, double *Sx) {
@@ -848,7 +851,7 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 			WSYNC();
 			if (fast) { // short lists: the moving operands stop at the last entry of the longer one (beyond a list's end: -inf entries)
 				const int mc = cntl[1] > cntl[2] ? cntl[1] : cntl[2];
-				for (int it = 0; it < ((mc + PER - 1) >> (6 - LOGNM)); it++) {
+				for (int it = 0, nit = __builtin_amdgcn_readfirstlane((mc + PER - 1) >> (6 - LOGNM)); it < nit; it++) {
 					const ListEnt eb1 = list_at(1, it * PER + (lane >> LOGNM)), eb2 = list_at(2, it * PER + (lane >> LOGNM));
 					__hip_atomic_fetch_max((double *)((char *)B0 + (ea0.t8 ^ eb1.t8)), ea0.v + eb1.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 					__hip_atomic_fetch_max((double *)((char *)B1 + (ea0.t8 ^ eb2.t8)), ea0.v + eb2.v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
