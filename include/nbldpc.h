@@ -343,6 +343,62 @@ nbl_status nbl_encode_batch(nbl_decoder *dec, const int32_t *msg, int32_t B, int
  * uint8.  For parity tests. */
 nbl_status nbl_read_transmitted(nbl_decoder *dec, int32_t slot, int32_t b0, int32_t n, int32_t *tx_msg, int32_t *tx_code, uint8_t *tx_index);
 
+/* ---- bit-LLR input and batched soft output ------------------------------------------------------------------------------------
+ * Bit <-> symbol LLR conversion around the message-passing core, per batch, on the device: for callers whose front end is not one of
+ * ours (an equaliser, an OFDM demapper, a fading channel) and for receivers that iterate around the decoder (turbo equalisation,
+ * iterative demapping, an outer code).  Defined here operation by operation, so that independent implementations agree
+ * (tests/soft_ref.py restates it in numpy).
+ *   A bit LLR is ln P(bit = 1) / P(bit = 0) -- the sign of the reference's RX_LLR_BIT.  Bit j of symbol a has value 2^j; q = 2^p.
+ *
+ * Bit-LLR input.  lam is [B][N p] doubles.  For every variable n and every a = 1 .. q-1:
+ *     s = 0.0;  for j = 0 .. p-1 ascending: if ((a >> j) & 1) s = s + lam[n p + j];  L_ch[n][a-1] = s
+ *   (Comm.cpp:362-372, which accumulates from 0).  Nothing else is done to the values; a punctured bit is the caller's 0.0.
+ *   nbl_decode_batch_bits / nbl_decode_batch_bits_device behave exactly as nbl_decode_batch / nbl_decode_batch_device on the expanded
+ *   L_ch: the same stream and synchronisation contract (the device form is enqueued on `stream` and not synchronised, except when
+ *   poll_every > 0), the same argument checks (NBL_ERR_ARG for a NULL decoder, input or out_sym, or B < 0; B == 0 is NBL_OK), on every
+ *   decoder kind: flooding, layered, layered-damped, nbl_create_ex, nbl_create_osd, and method 6 (which reads L_ch only).  No
+ *   demodulator has to be set.  Host -> device traffic is N p doubles per codeword instead of N (q - 1).
+ *
+ * Soft output of the LAST decode call (any of the decode entry points), for all B codewords of that call.
+ *   For codeword b let c2v be exactly what nbl_read_state returns for b, the reference's L_c2v at return: under early exit
+ *   (fixed_iters == 0) a codeword that converged at iteration k has the messages of iteration k-1 (zeros for k = 1); in every other
+ *   case the messages as the last iteration left them.  Then
+ *     P[n] = L_ch[n], then += c2v[e] for each edge e of n in n's edge order (AddLLRVector, the expression of NBLDPC.cpp:678-685);
+ *     P[n][0] = 0.
+ *     sym_llr[b][n][a-1] = P[n][a]
+ *     for bit j of n:  S1 = {a : (a >> j) & 1},  S0 = the rest, a = 0 (value 0.0) included;  M1 = max over S1,  M0 = max over S0
+ *       NBL_SOFT_MAXLOG:  bit_llr[b][n p + j] = M1 - M0
+ *       NBL_SOFT_LOGSUM:  bit_llr[b][n p + j] = (M1 + log(sum over S1, ascending a, of exp(P[a] - M1)))
+ *                                               - (M0 + log(sum over S0, ascending a, of exp(P[a] - M0)))
+ *       A difference that is zero is returned as +0.0 (the value written is the difference + 0.0), so the sign of a zero among the
+ *       P[a] never shows.
+ *   Max-log values are bit-identical between implementations; log-sum values agree to rounding only (device exp / log, and a tree
+ *   reduction where the definition sums in sequence).
+ *   Consequences:
+ *     - For a codeword that converged under early exit, P is the reference's L_post at return and DecideLLRVector(P[n]) == out_sym[n].
+ *     - For a codeword that did not converge, P is one check-node pass NEWER than the decision in out_sym (the reference, too, leaves
+ *       its loop after the check-node pass of the last iteration).
+ *     - With fixed_iters = 1, P is the state after max_iter iterations for every codeword, converged or not.
+ *     - OSD post-processing changes out_sym only, never the soft output.
+ *     - These are a-posteriori values.  Extrinsic values are the caller's subtraction of its own input.
+ *     - max_iter = 0 is legal: P = L_ch.
+ *   sym_llr [B][N][q-1] and bit_llr [B][N p]; either may be NULL (then it is not written), not both.
+ *   nbl_soft_output: host buffers; returns when they are filled.  nbl_soft_output_device: device buffers on the decoder's device; the
+ *   work is enqueued on `stream` (NULL = the decoder's own) and NOT synchronised; the caller orders it behind the decode: the same
+ *   stream, or poll_every > 0, which has synchronised already.  Nothing the call needs is read back to the host.
+ *   Refused with a message: NBL_ERR_ARG for both pointers NULL, an unknown metric, or no decode call on this handle yet;
+ *   NBL_ERR_UNSUPPORTED on a method-6 decoder (it runs no iterations: there are no messages).
+ *   Costs nothing unless called; needs neither nbl_set_record_state nor any other preparation. */
+nbl_status nbl_decode_batch_bits(nbl_decoder *dec, const double *bit_llr /* HOST [B][N p] */, int32_t B, int32_t *out_sym,
+                                 uint8_t *converged, int32_t *iters);
+nbl_status nbl_decode_batch_bits_device(nbl_decoder *dec, const double *d_bit_llr, int32_t B, int32_t *d_out_sym, uint8_t *d_converged,
+                                        int32_t *d_iters, void *stream);
+#define NBL_SOFT_LOGSUM 0
+#define NBL_SOFT_MAXLOG 1
+nbl_status nbl_soft_output(nbl_decoder *dec, int32_t metric, double *sym_llr /* HOST [B][N][q-1] or NULL */,
+                           double *bit_llr /* HOST [B][N p] or NULL */);
+nbl_status nbl_soft_output_device(nbl_decoder *dec, int32_t metric, double *d_sym_llr, double *d_bit_llr, void *stream);
+
 /* Message state of codeword b after the last decode call (host buffers, any may be NULL):
  * post [N][q-1], v2c [E][q-1], c2v [E][q-1], edges in variable-major order.  For parity tests.
  * post and c2v are the reference's members at return.  v2c differs for a codeword that CONVERGED at iteration k >= 2: the

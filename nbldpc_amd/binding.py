@@ -15,13 +15,14 @@ LIB_PATH = os.environ.get("NBL_HIP_LIB") or os.path.join(_HERE, "csrc", "libnbld
 
 METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
+SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
 
 # every symbol include/nbldpc.h declares
 EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
-           "nbl_workspace_bytes")
+           "nbl_workspace_bytes", "nbl_decode_batch_bits", "nbl_decode_batch_bits_device", "nbl_soft_output", "nbl_soft_output_device")
 
 
 class NblError(RuntimeError):
@@ -93,6 +94,14 @@ def load_library():
         L.nbl_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_decode_batch_device.restype = C.c_int
         L.nbl_decode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_bits.restype = C.c_int
+        L.nbl_decode_batch_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_bits_device.restype = C.c_int
+        L.nbl_decode_batch_bits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_soft_output.restype = C.c_int
+        L.nbl_soft_output.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.nbl_soft_output_device.restype = C.c_int
+        L.nbl_soft_output_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_read_state.restype = C.c_int
         L.nbl_read_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_set_record_state.argtypes = [C.c_void_p, C.c_int32]
@@ -251,6 +260,44 @@ class Decoder:
     def decode_device(self, d_L_ch, B, d_out, d_conv=None, d_iters=None, stream=None):
         """Raw device pointers (ints); asynchronous on `stream` (a hipStream_t as int, None = decoder stream)."""
         self._chk(self.lib.nbl_decode_batch_device(self.h, d_L_ch, B, d_out, d_conv, d_iters, stream))
+
+    def decode_bits(self, bit_llr):
+        """bit_llr: host array [B][N p] float64, ln P(bit = 1) / P(bit = 0), bit j of a symbol has value 2^j -> (out, converged, iters);
+        L_ch is expanded on the device (nbl_decode_batch_bits)"""
+        bit_llr = np.ascontiguousarray(bit_llr, dtype=np.float64)
+        B = bit_llr.shape[0]
+        assert bit_llr.shape == (B, self.code.N * (self.code.q.bit_length() - 1)), bit_llr.shape
+        out = np.zeros((B, self.code.N), dtype=np.int32)
+        conv = np.zeros(B, dtype=np.uint8)
+        iters = np.zeros(B, dtype=np.int32)
+        self._chk(self.lib.nbl_decode_batch_bits(self.h, bit_llr.ctypes.data, B, out.ctypes.data, conv.ctypes.data, iters.ctypes.data))
+        return out, conv, iters
+
+    def decode_bits_device(self, d_bit_llr, B, d_out, d_conv=None, d_iters=None, stream=None):
+        """Raw device pointers (ints); asynchronous on `stream` (a hipStream_t as int, None = decoder stream)."""
+        self._chk(self.lib.nbl_decode_batch_bits_device(self.h, d_bit_llr, B, d_out, d_conv, d_iters, stream))
+
+    def soft_output(self, metric="maxlog", sym=True, bits=True, B=None):
+        """A-posteriori LLRs of the last decode call (nbl_soft_output): (sym_llr [B][N][q-1] | None, bit_llr [B][N p] | None).
+        metric: "maxlog" / "logsum" or SOFT_MAXLOG / SOFT_LOGSUM.  B: the batch of that call; needed only when the call did not go
+        through this object's decode methods (the device forms)."""
+        m = {"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(metric, metric)
+        B = max(self._last_B() if B is None else B, 1)       # (before the first decode the call is refused; the buffers only have to exist)
+        S = np.zeros((B, self.code.N, self.code.q - 1)) if sym else None
+        Lb = np.zeros((B, self.code.N * (self.code.q.bit_length() - 1))) if bits else None
+        self._chk(self.lib.nbl_soft_output(self.h, int(m), S.ctypes.data if sym else None, Lb.ctypes.data if bits else None))
+        return S, Lb
+
+    def soft_output_device(self, metric, d_sym_llr, d_bit_llr, stream=None):
+        """Raw device pointers (ints, None = that output is not wanted); enqueued on `stream`, not synchronised."""
+        m = {"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(metric, metric)
+        self._chk(self.lib.nbl_soft_output_device(self.h, int(m), d_sym_llr, d_bit_llr, stream))
+
+    def _last_B(self):
+        """batch size of the last decode call (nbl_debug_last_batch; 0 before the first)"""
+        self.lib.nbl_debug_last_batch.restype = C.c_int32
+        self.lib.nbl_debug_last_batch.argtypes = [C.c_void_p]
+        return int(self.lib.nbl_debug_last_batch(self.h))
 
     def set_demodulator(self, mod_order, n_mod_sym, src, constellation=None, metric=None, force_general=False):
         """src: int32 sample index per code bit (BPSK) / per code symbol (q-ary), -1 = punctured.  Any other order (and every order

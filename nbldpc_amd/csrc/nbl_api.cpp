@@ -60,6 +60,10 @@ struct nbl_decoder {
 	NblDemodPoint *d_dmdesc = nullptr; // [N][p + 1]
 	double *d_rx = nullptr;
 	size_t d_rx_cap = 0;
+	// bit-LLR input and soft output (nbl_decode_batch_bits, nbl_soft_output): staging of the host forms, grown on demand
+	double *d_lam = nullptr, *d_soft_sym = nullptr, *d_soft_bit = nullptr;
+	size_t d_lam_cap = 0, d_soft_sym_cap = 0, d_soft_bit_cap = 0;
+	size_t soft_bytes = 0;      // their sum: part of nbl_workspace_bytes from the moment they exist
 	// device-side AWGN channel (nbl_decode_batch_noise)
 	std::vector<double> h_cons;  // constellation as given to nbl_set_demodulator
 	uint32_t *d_jump = nullptr;  // [3][L] A^(4 s) mod m of the three generators
@@ -179,6 +183,8 @@ static void free_workspace(nbl_decoder *d)
 	d->d_conv8 = nullptr;
 	d->cap = 0;
 	d->ws_bytes = 0;
+	d->last_B = 0; // (nothing of the last decode call is left to read)
+	d->last_c2v = nullptr;
 }
 
 static bool small_enabled()
@@ -237,7 +243,7 @@ extern "C" const char *nbl_last_error(const nbl_decoder *dec)
 	return both.c_str();
 }
 
-extern "C" size_t nbl_workspace_bytes(const nbl_decoder *dec) { return dec ? dec->ws_bytes : 0; }
+extern "C" size_t nbl_workspace_bytes(const nbl_decoder *dec) { return dec ? dec->ws_bytes + dec->soft_bytes : 0; }
 
 static nbl_status fail_create(nbl_decoder *d, nbl_status st, const std::string &msg)
 {
@@ -764,6 +770,8 @@ extern "C" void nbl_destroy(nbl_decoder *d)
 	if (d->d_cons) (void)hipFree(d->d_cons);
 	if (d->d_dmdesc) (void)hipFree(d->d_dmdesc);
 	if (d->d_rx) (void)hipFree(d->d_rx);
+	for (double *p : {d->d_lam, d->d_soft_sym, d->d_soft_bit})
+		if (p) (void)hipFree(p);
 	for (double *p : d->d_rxs)
 		if (p) (void)hipFree(p);
 	if (d->stream2) { (void)hipStreamSynchronize(d->stream2); (void)hipStreamDestroy(d->stream2); }
@@ -1267,6 +1275,122 @@ extern "C" nbl_status nbl_decode_batch_samples(nbl_decoder *d, const double *rx,
 	return NBL_OK;
 }
 
+// ---- bit-LLR input and batched soft output (nbl_soft.hip) ------------------------------------------------
+
+// a staging buffer grown on demand, like d_rx; counted in nbl_workspace_bytes from the moment it exists
+static nbl_status grow_staging(nbl_decoder *d, double **buf, size_t *cap, size_t bytes)
+{
+	if (bytes <= *cap) return NBL_OK;
+	if (*buf) (void)hipFree(*buf);
+	*buf = nullptr;
+	d->soft_bytes -= *cap;
+	*cap = 0;
+	HIP_TRY(d, hipMalloc((void **)buf, bytes));
+	*cap = bytes;
+	d->soft_bytes += bytes;
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_decode_batch_bits_device(nbl_decoder *d, const double *d_bit_llr, int32_t B, int32_t *d_out_sym,
+                                                   uint8_t *d_converged, int32_t *d_iters, void *stream)
+{
+	if (!d || !d_bit_llr || !d_out_sym || B < 0) return NBL_ERR_ARG;
+	if (B == 0) return NBL_OK;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	hipStream_t st = stream ? (hipStream_t)stream : d->stream;
+	nbl_status s = ensure_workspace(d, B);
+	if (s) return s;
+	HIP_TRY(d, nbl_launch_bits_to_lch(d_bit_llr, d->g, d->w, B, st));
+	if ((s = run_iterations(d, nullptr, B, st))) return s; // (L_ch is in place: init_kernel leaves it alone)
+	HIP_TRY(d, hipMemcpyAsync(d_out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToDevice, st));
+	if (d_converged) HIP_TRY(d, hipMemcpyAsync(d_converged, d->w.done, (size_t)B, hipMemcpyDeviceToDevice, st));
+	if (d_iters) HIP_TRY(d, hipMemcpyAsync(d_iters, d->w.iters, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_decode_batch_bits(nbl_decoder *d, const double *bit_llr, int32_t B, int32_t *out_sym, uint8_t *converged,
+                                            int32_t *iters)
+{
+	if (!d || !bit_llr || !out_sym || B < 0) return NBL_ERR_ARG;
+	if (B == 0) return NBL_OK;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	nbl_status s = ensure_workspace(d, B);
+	if (s) return s;
+	const size_t bytes = (size_t)B * d->g.N * d->g.p * 8;
+	if ((s = grow_staging(d, &d->d_lam, &d->d_lam_cap, bytes))) return s;
+	HIP_TRY(d, hipMemcpyAsync(d->d_lam, bit_llr, bytes, hipMemcpyHostToDevice, d->stream));
+	HIP_TRY(d, nbl_launch_bits_to_lch(d->d_lam, d->g, d->w, B, d->stream));
+	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
+	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
+	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->w.done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
+	if (iters) HIP_TRY(d, hipMemcpyAsync(iters, d->w.iters, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	return NBL_OK;
+}
+
+// Diagnostic only (not part of include/nbldpc.h): the batch size of the last decode call -- what nbl_soft_output's buffers are sized by
+extern "C" int32_t nbl_debug_last_batch(const nbl_decoder *d) { return d ? d->last_B : 0; }
+
+// what nbl_soft_output refuses, before the device is touched
+static nbl_status soft_check(nbl_decoder *d, int32_t metric, const double *sym_llr, const double *bit_llr)
+{
+	if (!d) return NBL_ERR_ARG;
+	if (d->prm.method == NBL_METHOD_OSD) { d->err = "nbl_soft_output: an OSD-only decoder (method 6) runs no iterations: there are no messages to form a posterior from"; return NBL_ERR_UNSUPPORTED; }
+	if (!sym_llr && !bit_llr) { d->err = "nbl_soft_output: sym_llr and bit_llr are both NULL"; return NBL_ERR_ARG; }
+	if (metric != NBL_SOFT_LOGSUM && metric != NBL_SOFT_MAXLOG) {
+		d->err = "nbl_soft_output: unknown metric " + std::to_string(metric) + " (NBL_SOFT_LOGSUM = 0, NBL_SOFT_MAXLOG = 1)";
+		return NBL_ERR_ARG;
+	}
+	if (d->last_B <= 0 || !d->w.Lch) { d->err = "nbl_soft_output: no decode call has run on this handle yet"; return NBL_ERR_ARG; }
+	return NBL_OK;
+}
+
+// Where the c2v of the last decode call are: nbl_read_state's choice (below), handed to the kernel as a rule instead of being made per
+// codeword on the host.
+static NblSoftSrc soft_src(const nbl_decoder *d)
+{
+	NblSoftSrc s{};
+	s.bufA = d->w.c2v;
+	s.bufB = d->c2v_alt;
+	s.zeros = d->c2v_zero;
+	s.last = d->last_c2v ? d->last_c2v : d->w.c2v;
+	s.last_shared = (d->c2v_zero && s.last == d->c2v_zero) ? 1 : 0;
+	s.per_codeword = (d->last_fused && d->c2v_alt && !d->prm.fixed_iters) ? 1 : 0;
+	s.done = d->w.done;
+	s.iters = d->w.iters;
+	return s;
+}
+
+extern "C" nbl_status nbl_soft_output_device(nbl_decoder *d, int32_t metric, double *d_sym_llr, double *d_bit_llr, void *stream)
+{
+	nbl_status s = soft_check(d, metric, d_sym_llr, d_bit_llr);
+	if (s) return s;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	hipStream_t st = stream ? (hipStream_t)stream : d->stream;
+	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, d_sym_llr, d_bit_llr, st));
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_soft_output(nbl_decoder *d, int32_t metric, double *sym_llr, double *bit_llr)
+{
+	nbl_status s = soft_check(d, metric, sym_llr, bit_llr);
+	if (s) return s;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	const size_t B = (size_t)d->last_B, N = d->g.N;
+	const size_t sym_bytes = B * N * (d->g.q - 1) * 8, bit_bytes = B * N * d->g.p * 8;
+	if (sym_llr && (s = grow_staging(d, &d->d_soft_sym, &d->d_soft_sym_cap, sym_bytes))) return s;
+	if (bit_llr && (s = grow_staging(d, &d->d_soft_bit, &d->d_soft_bit_cap, bit_bytes))) return s;
+	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, sym_llr ? d->d_soft_sym : nullptr,
+	                                  bit_llr ? d->d_soft_bit : nullptr, d->stream));
+	if (sym_llr) HIP_TRY(d, hipMemcpyAsync(sym_llr, d->d_soft_sym, sym_bytes, hipMemcpyDeviceToHost, d->stream));
+	if (bit_llr) HIP_TRY(d, hipMemcpyAsync(bit_llr, d->d_soft_bit, bit_bytes, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	return NBL_OK;
+}
 
 // ---- AWGN channel + CRand on the device ------------------------------------------------------------------
 

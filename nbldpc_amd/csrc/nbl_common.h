@@ -79,6 +79,18 @@ struct NblLayerDev {
 	                 // [1] n's degree dv, [4 .. 4 + dv - 1] the c2v slots (check-major positions) of n's edges in n's edge order
 };
 
+// soft output (nbl_soft.hip): where the c2v messages of the last decode call are, and the rule that picks the buffer per codeword
+struct NblSoftSrc {
+	const double *bufA, *bufB;      // the two c2v buffers of the fused (double-buffered) path; iteration i writes bufB when i is odd
+	const double *zeros;            // the shared all-zero [E][q] block that stands for iteration 0 (may be NULL)
+	const double *last;             // the buffer the last launched iteration wrote (what a codeword that did not stop early holds)
+	int last_shared;                // 1: `last` is that one shared block (no iteration ran), not a [B][E][q] buffer
+	int per_codeword;               // 1: fused path under early exit -- a codeword with done[b] reads the buffer iteration iters[b] - 1
+	                                // wrote, the zeros when that is iteration 0 (nbl_read_state's rule); 0: every codeword reads `last`
+	const uint8_t *done;
+	const int *iters;
+};
+
 struct NblRun {
 	int B;                          // codeword slots the grid covers (= batch size unless w.active is set, then an upper bound of *w.n_act)
 	int iter, fixed_iters;

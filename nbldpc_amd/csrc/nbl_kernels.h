@@ -64,6 +64,13 @@ hipError_t nbl_launch_cn_ems64(const NblGraphDev &g, const NblWork &w, const Nbl
 // log-QSPA check node for GF(64), check degree 4: four checks per wave, four symbols per lane (nbl_cn_bp64.hip)
 hipError_t nbl_launch_cn_bp64(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);
 
+// bit <-> symbol LLR conversion around the iterations (nbl_soft.hip): per-bit LLRs [B][N p] -> w.Lch; and the a-posteriori vectors of
+// the last decode call, unpadded [B][N][q-1], with their bit marginals [B][N p] (metric: NBL_SOFT_* of include/nbldpc.h; either output
+// may be NULL)
+hipError_t nbl_launch_bits_to_lch(const double *d_lam, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
+hipError_t nbl_launch_soft_output(const NblGraphDev &g, const double *d_Lch, const NblSoftSrc &src, int B, int metric, double *d_sym_llr,
+                                  double *d_bit_llr, hipStream_t st);
+
 // AWGN channel + CRand on the device (nbl_noise.hip)
 hipError_t nbl_launch_noise_gen(const uint32_t *state, const uint32_t *jump, int L, int B, double *fn, uint32_t *flag_idx, double *flag_arg,
                                 unsigned *flag_count, unsigned cap, hipStream_t st);

@@ -246,6 +246,22 @@ int CNBLDPC::DecodingBatchSamples(const double *rx, double sigma, int B, int *ou
 	return 0;
 }
 
+int CNBLDPC::DecodingBatchBits(const double *bit_llr, int B, int *out, uint8_t *converged, int *iters)
+{
+	if (!dec) { error = "decoder not initialised"; return -1; }
+	nbl_status st = nbl_decode_batch_bits(dec, bit_llr, B, out, converged, iters);
+	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
+	return 0;
+}
+
+int CNBLDPC::SoftOutput(int metric, double *sym_llr, double *bit_llr)
+{
+	if (!dec) { error = "decoder not initialised"; return -1; }
+	nbl_status st = nbl_soft_output(dec, metric, sym_llr, bit_llr);
+	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
+	return 0;
+}
+
 int CNBLDPC::DecodingBatchNoise(const unsigned char *tx_index, const unsigned int *lane_state, double sigma, int B, int *out, uint8_t *converged, int *iters)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }

@@ -39,6 +39,12 @@ public:
 	// device-side demodulation (replaces CComm::Demodulate, Comm.cpp:340-407): rx [B][L][2] received samples
 	int SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src, int metric = 0); // metric: NBL_DEMOD_*, general orders only
 	int DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters);
+	// per-bit LLRs in place of symbol LLRs (the RX_LLR_BIT -> RX_LLR_SYM loop of Comm.cpp:359-373 runs on the device): bit_llr [B][CodeLen p],
+	// ln P(bit = 1) / P(bit = 0), bit j of a symbol has value 2^j, a punctured bit is 0.0.  No demodulator has to be set.
+	int DecodingBatchBits(const double *bit_llr, int B, int *out, uint8_t *converged, int *iters);
+	// a-posteriori LLRs of the last Decoding* call, all B codewords: sym_llr [B][CodeLen][GFq-1] and / or bit_llr [B][CodeLen p] (either
+	// may be null, not both); metric: NBL_SOFT_* (0 log-sum, 1 max-log).  Defined in include/nbldpc.h.
+	int SoftOutput(int metric, double *sym_llr, double *bit_llr);
 	// device-side channel (replaces CComm::Channel_AWGN + CRand, Comm.cpp:328-337 / Rand.cpp:17-37): tx_index [B][L] constellation
 	// indices, lane_state [B][3] generator states in front of the frame
 	int DecodingBatchNoise(const unsigned char *tx_index, const unsigned int *lane_state, double sigma, int B, int *out, uint8_t *converged, int *iters);
