@@ -813,7 +813,7 @@ extern "C" int32_t nbl_debug_graph_windows(nbl_decoder *d)
 }
 
 // Diagnostic only (not part of include/nbldpc.h): in-kernel cycle stamps of the check-node kernel.
-extern "C" nbl_status nbl_debug_stamps(nbl_decoder *d, int32_t on, unsigned long long out[16])
+extern "C" nbl_status nbl_debug_stamps(nbl_decoder *d, int32_t on, unsigned long long out[NBL_STAMP_SLOTS])
 {
 	if (!d) return NBL_ERR_ARG;
 	d->err.clear();
@@ -821,15 +821,15 @@ extern "C" nbl_status nbl_debug_stamps(nbl_decoder *d, int32_t on, unsigned long
 	if (out && d->w.stamps) {
 		HIP_TRY(d, hipStreamSynchronize(d->stream));
 		HIP_TRY(d, hipDeviceSynchronize());
-		HIP_TRY(d, hipMemcpy(out, d->w.stamps, 16 * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(d, hipMemcpy(out, d->w.stamps, NBL_STAMP_SLOTS * 8, hipMemcpyDeviceToHost));
 	}
 	if (on && !d->w.stamps) {
 		void *p = nullptr;
-		HIP_TRY(d, hipMalloc(&p, 16 * 8));
+		HIP_TRY(d, hipMalloc(&p, NBL_STAMP_SLOTS * 8));
 		d->graph_allocs.push_back(p);
 		d->w.stamps = (unsigned long long *)p;
 	}
-	if (d->w.stamps && on) HIP_TRY(d, hipMemset(d->w.stamps, 0, 16 * 8));
+	if (d->w.stamps && on) HIP_TRY(d, hipMemset(d->w.stamps, 0, NBL_STAMP_SLOTS * 8));
 	if (!on) d->w.stamps = nullptr;
 	return NBL_OK;
 }

@@ -26,6 +26,9 @@
 #ifndef NBL_EMS_PRUNE
 #define NBL_EMS_PRUNE 1 // the exact bound on the gather lists (0: every entry, for A/B runs)
 #endif
+#ifndef NBL_EMS_ND
+#define NBL_EMS_ND 1 // short-list checks on which at most one edge can still deviate go straight to the emit stage (0: they run the short-list code, for A/B runs)
+#endif
 #include <type_traits>
 #include "nbl_device.h"
 #include "nbl_kernels.h"
@@ -316,7 +319,10 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 	const bool st_on = (w.stamps != nullptr) && ((blockIdx.x & 63) == 0);
 #define STAMP(i) do { if (st_on) { unsigned long long t1_ = clock64(); st_acc[i] += t1_ - st_t0; st_t0 = t1_; } } while (0)
 #define STAMP_COUNT(i) do { if (st_on) st_acc[i]++; } while (0)
-	if (st_on) st_t0 = clock64();
+	const unsigned long long st_begin = st_on ? clock64() : 0;
+	unsigned long long st_mid = 0; // the clock where the short-list class is known
+	int st_cls = 6;                // 0..4: short lists with nd deviating edges; 5: gate on, bounds failed; 6: gate off
+	st_t0 = st_begin;
 #elif defined(NBL_EMS_MARKS)
 	// static instruction budget (tools/isa_budget.py): a comment line in the ISA at every section boundary
 #define STAMP(i) asm volatile("; NBLMARK " #i)
@@ -525,6 +531,7 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 	// are built from one compare per symbol, without histogram and cut search, and every later loop runs over the short lists.  On a
 	// converged codeword (one dominant symbol per edge) that leaves a handful of entries.  Otherwise the full selection runs as before.
 	bool fast = false;
+	int nd = 4; // edges with two or more entries at or above their threshold (short lists only)
 	double thr[4] = {0, 0, 0, 0};
 #if NBL_EMS_PRUNE
 	if (tryf) {
@@ -553,13 +560,30 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 			cntl[j] = c;
 			fast = fast && c <= nmr;
 		}
-		if (!fast) cntl[0] = cntl[1] = cntl[2] = cntl[3] = nmr;
+		// An edge with at most one entry at or above its threshold cannot deviate usefully: that entry is its rank 0.  nd = the edges
+		// that still can.  A configuration outside conf(q,1) deviates on two or more of an output's three other edges, so with nd <= 1
+		// none exists for any output: S[] is final, and everything between here and the emit stage is left out (bit-exact: a
+		// configuration with one deviation equals its conf(q,1) term, both sum the three other edges in index order).
+		nd = (cntl[0] >= 2) + (cntl[1] >= 2) + (cntl[2] >= 2) + (cntl[3] >= 2);
+		if (!fast) { cntl[0] = cntl[1] = cntl[2] = cntl[3] = nmr; nd = 4; }
 #ifdef NBL_EMS_STAMPS
 		if (st_on) { st_acc[13] += fast ? 1 : 0; st_acc[14] += cntl[0] + cntl[1] + cntl[2] + cntl[3]; } // short-list checks, list entries
+		if (w.stamps) st_cls = fast ? nd : 5;
 #endif
 	}
 #endif
-	if (NC >= 2) { // conf(nm,1) needs no lists: it is contained in conf(q,1)
+#ifdef NBL_EMS_STAMPS
+	if (st_on) st_mid = clock64();
+#endif
+	// (wave-uniform `if`s around the middle of the kernel, not an exit: the 24 loads above stay hoisted.  nd is 4 without short lists.
+	// The fused instances test that scalar integer at both places: held as a boolean -- a scalar register PAIR across the selection,
+	// which has none to spare -- the class costs them a third of the gain (+0.85 % instead of +1.3 % on the headline); the unfused
+	// instances hold the boolean: the integer costs them two scalar spills)
+	constexpr int ND_SKIP = NBL_EMS_ND ? 1 : -1;
+	const bool skip_held = !FUSED && NBL_EMS_ND && fast && nd <= 1;
+#define ND_SKIPPED (FUSED ? nd <= ND_SKIP : skip_held)
+#define ND_KEPT (FUSED ? nd > ND_SKIP : !skip_held) // (its own comparison: the compiler would hold the negated one as a boolean)
+	if (NC >= 2 && ND_KEPT) { // conf(nm,1) needs no lists: it is contained in conf(q,1)
 		// list members (wave-uniform masks per slot) -> the list image: slots 0, 2 hold even symbols, slots 1, 3 odd ones
 		auto compact = [&](int j, const uint64_t (&member)[4]) {
 			const int c0n = __popcll(member[0]), c2n = __popcll(member[2]), c1n = __popcll(member[1]);
@@ -839,7 +863,9 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 		dst[64 + lane] = o23;
 	};
 
-	if (NC >= 3) {
+	if (ND_SKIPPED) {
+		// nothing beyond conf(q,1) can matter
+	} else if (NC >= 3) {
 		// the three pair convolutions in one pass: B0 = e0 (+) e1, B1 = e0 (+) e2, B2 = e1 (+) e2
 		{
 			double2 ninf;
@@ -900,6 +926,9 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 		STAMP(6);
 	}
 	WSYNC();
+#ifdef NBL_EMS_STAMPS
+	const unsigned long long st_emit = st_on ? clock64() : 0;
+#endif
 	emit_stage(3, B0);
 	emit_stage(2, B1);
 	emit_stage(1, B2);
@@ -917,11 +946,18 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 	if (st_on && lane == 0) {
 		for (int i = 0; i < 15; i++) atomicAdd(&w.stamps[i], st_acc[i]);
 		atomicAdd(&w.stamps[15], 1ull);
+		// by short-list class: sampled checks, their wave cycles, their cycles between the bounds and the emit stage
+		atomicAdd(&w.stamps[16 + st_cls], 1ull);
+		atomicAdd(&w.stamps[24 + st_cls], st_t0 - st_begin);
+		atomicAdd(&w.stamps[32 + st_cls], st_emit - st_mid);
 	}
+	if (w.stamps && lane == 0) atomicAdd(&w.stamps[40 + st_cls], 1ull); // the classes of ALL checks (the cycles above: of the sampled blocks)
 #endif
 #undef STAMP
 #undef STAMP_COUNT
 #undef TOFF
+#undef ND_SKIPPED
+#undef ND_KEPT
 }
 
 bool nbl_ems256_applicable(const NblShape &s, int nm, int nc)

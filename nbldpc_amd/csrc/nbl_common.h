@@ -55,6 +55,10 @@ struct NblDemodPoint {
 	int32_t nown;
 };
 
+// slots of the debug stamps (nbl_debug_stamps): 0..15 the sections and counts of the check-node kernels, 16..47 the short-list
+// classes of the GF(256) EMS kernel (eight slots each: sampled checks, their wave cycles, their cycles between the bounds and the
+// emit stage, checks of all blocks)
+#define NBL_STAMP_SLOTS 48
 struct NblWork {
 	double *Lch, *v2c, *c2v, *post; // post only when state recording is on
 	const double *c2v_prev;         // fused EMS iteration: c2v of the previous iteration (read), c2v = this iteration (written)
@@ -67,7 +71,7 @@ struct NblWork {
 	const int *active;              // early exit, large batches: codewords still iterating, ascending, rebuilt after every window of
 	                                // iterations (NULL = every codeword has its own slot); grids then cover r.B SLOTS, not codewords
 	const int *n_act;               // number of valid entries of `active`
-	unsigned long long *stamps;     // [16] debug: per-section cycle sums of the check-node kernel (NULL = off)
+	unsigned long long *stamps;     // [NBL_STAMP_SLOTS] debug: per-section cycle sums of the check-node kernel (NULL = off)
 };
 
 // layered (check-serial) schedule, nbl_create_layered (nbl_cn_layered.hip)

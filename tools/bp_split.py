@@ -29,7 +29,7 @@ for it in (1, 2, 3, 4, 6, 8, 12, 20, 40, 100):
     dec = nb.Decoder(code, nb.METHOD_BP, it, fixed_iters=1, max_batch=B)
     lib = dec.lib
     lib.nbl_debug_stamps.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    out = (C.c_ulonglong * 16)()
+    out = (C.c_ulonglong * 48)()  # NBL_STAMP_SLOTS
     lib.nbl_debug_stamps(dec.h, 1, None)
     _, conv, _ = dec.decode(L)
     lib.nbl_debug_stamps(dec.h, 0, out)
