@@ -380,7 +380,7 @@ nbl_status nbl_read_transmitted(nbl_decoder *dec, int32_t slot, int32_t b0, int3
  *       its loop after the check-node pass of the last iteration).
  *     - With fixed_iters = 1, P is the state after max_iter iterations for every codeword, converged or not.
  *     - OSD post-processing changes out_sym only, never the soft output.
- *     - These are a-posteriori values.  Extrinsic values are the caller's subtraction of its own input.
+ *     - These are a-posteriori values.  Symbol-level extrinsic values are nbl_soft_output_ex's (below).
  *     - max_iter = 0 is legal: P = L_ch.
  *   sym_llr [B][N][q-1] and bit_llr [B][N p]; either may be NULL (then it is not written), not both.
  *   nbl_soft_output: host buffers; returns when they are filled.  nbl_soft_output_device: device buffers on the decoder's device; the
@@ -398,6 +398,69 @@ nbl_status nbl_decode_batch_bits_device(nbl_decoder *dec, const double *d_bit_ll
 nbl_status nbl_soft_output(nbl_decoder *dec, int32_t metric, double *sym_llr /* HOST [B][N][q-1] or NULL */,
                            double *bit_llr /* HOST [B][N p] or NULL */);
 nbl_status nbl_soft_output_device(nbl_decoder *dec, int32_t metric, double *d_sym_llr, double *d_bit_llr, void *stream);
+
+/* ---- iterative demapping: bit priors for the general demodulator, extrinsic soft output, and the loop between them -----------------
+ * A receiver whose constellation does not match the field (M != q) can feed the decoder's knowledge of the OTHER symbols' bits back
+ * into the demodulator (BICM-ID).  Nothing in the reference computes any of this; the operations are defined here, operation by
+ * operation, so that independent implementations agree (tests/idd_ref.py restates them in numpy, with a probability-domain brute
+ * force beside the demodulator).  Sign and bit order are the soft output's: a bit LLR is
+ * ln P(bit = 1) / P(bit = 0), bit j of symbol a has value 2^j.
+ *
+ * Prior-aware general demodulator.  prior is [B][N p] doubles, indexed by code bit g = n p + j.  Everything of the general
+ * demodulator above stays; only the distance of table point c at point s, as seen by symbol n, changes:
+ *     A_s,n(c) = 0.0;  for label position i = 0 .. m-1 ascending:
+ *                    if i is foreign to n at s, AND some code bit g claims label bit t = s m + i (src[g] == t), AND bit i of c
+ *                    (weight 2^(m-1-i)) is 1:   A = A + prior[b][g]
+ *     d'_s,n(c) = d_s(c) - (2 sigma sigma) * A_s,n(c)
+ *   d' replaces d in both metrics: the minimum, the dmin of log-sum, and the exponent.  Own positions never contribute, so the result
+ *   is extrinsic with respect to symbol n's own bits; unclaimed label bits stay uniform; a prior of all 0.0 gives d' = d exactly and
+ *   LLRs bit-identical to the prior-less path.  Non-finite priors are the caller's problem.
+ *   nbl_decode_batch_samples_prior: nbl_decode_batch_samples with that demodulator.  prior == NULL IS nbl_decode_batch_samples and
+ *   launches the kernel that call launches.  A BPSK or q-ary demodulator that is not forced general has no foreign position: a prior
+ *   is accepted and inert there.
+ *
+ * Extrinsic soft output.  nbl_soft_output_ex / nbl_soft_output_device_ex with flags == 0 ARE nbl_soft_output / nbl_soft_output_device.
+ *   NBL_SOFT_EXTRINSIC: P[n] starts from the all-0.0 vector instead of L_ch[n]; everything else of the soft output's definition holds
+ *   word for word -- the choice of c2v per codeword, the edge order, the +0.0 rule -- on every decoder kind the existing call works
+ *   on, with the same refusals plus NBL_ERR_ARG for an unknown flag bit.  (The bit marginals of the symbol-level extrinsic cannot be
+ *   had by subtracting bit LLRs, hence the call.)
+ *
+ * The loop.  Per codeword b, independently of every other codeword of the batch:
+ *     prior_1 = all 0.0
+ *     for k = 1 .. passes:
+ *         L_ch = the prior-aware demodulator of b's samples with prior_k
+ *         decode exactly as one nbl_decode_batch_samples call does from that L_ch (messages start from zero; max_iter, fixed_iters,
+ *             poll_every, OSD as the decoder was created)
+ *         if converged, or k == passes:  out_sym, converged, iters are this pass's;  passes_used[b] = k;  stop
+ *         prior_{k+1} = the extrinsic bit LLRs (NBL_SOFT_EXTRINSIC, soft_metric) of this pass's state
+ *   passes == 1 IS the plain call, bit for bit.  Passes 2 and later run on the codewords still unconverged only, gathered into dense
+ *   buffers, with grids sized to them; the survivor count is read back after every pass that has a successor: ONE host
+ *   synchronisation per pass, also where poll_every == 0.  The caller's samples and a slot's samples are never overwritten.
+ *   With max-log metrics on both sides every output is bit-identical between implementations; under log-sum one rounding can flip a
+ *   convergence, so only a single pass from a given prior is comparable.
+ *   nbl_decode_batch_samples_idd: host samples, as nbl_decode_batch_samples.  nbl_decode_batch_resident_idd: the samples a slot
+ *   holds, as nbl_decode_batch_resident; it leaves the final words where nbl_count_errors reads them and out_sym may be NULL once a
+ *   transmitter is set.  passes_used [B] may be NULL.
+ *   Refused with a message, before the device is touched: NBL_ERR_ARG for a NULL idd, passes < 1, an unknown soft_metric, or no
+ *   demodulator set; NBL_ERR_UNSUPPORTED for passes > 1 on a method-6 decoder (it has no messages).  On a BPSK or q-ary demodulator
+ *   that is not forced general the later passes are provably the same decode: pass 1 runs alone and a codeword that did not converge
+ *   reports passes_used = passes.
+ *   After a loop call with passes > 1 on a general demodulator the workspace holds a sub-batch: until the next ordinary decode call
+ *   nbl_soft_output* and nbl_read_state are refused (NBL_ERR_ARG, the message says why), and nbl_last_timing describes the last
+ *   pass's sub-batch decode alone, not the call.  A plain decode afterwards behaves as if the loop call had never happened.  The loop's buffers grow on demand and count in nbl_workspace_bytes. */
+#define NBL_SOFT_EXTRINSIC 1u
+typedef struct nbl_idd_params {
+	int32_t passes;              /* >= 1 */
+	int32_t soft_metric;         /* NBL_SOFT_*: the metric of the extrinsic bit LLRs between passes */
+} nbl_idd_params;
+nbl_status nbl_decode_batch_samples_prior(nbl_decoder *dec, const double *rx, const double *prior /* HOST [B][N p] or NULL */, double sigma,
+                                          int32_t B, int32_t *out_sym, uint8_t *converged, int32_t *iters);
+nbl_status nbl_soft_output_ex(nbl_decoder *dec, int32_t metric, uint32_t flags, double *sym_llr, double *bit_llr);
+nbl_status nbl_soft_output_device_ex(nbl_decoder *dec, int32_t metric, uint32_t flags, double *d_sym_llr, double *d_bit_llr, void *stream);
+nbl_status nbl_decode_batch_samples_idd(nbl_decoder *dec, const double *rx, double sigma, int32_t B, const nbl_idd_params *idd,
+                                        int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used /* [B] or NULL */);
+nbl_status nbl_decode_batch_resident_idd(nbl_decoder *dec, int32_t slot, double sigma, int32_t B, const nbl_idd_params *idd,
+                                         int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used /* [B] or NULL */);
 
 /* Message state of codeword b after the last decode call (host buffers, any may be NULL):
  * post [N][q-1], v2c [E][q-1], c2v [E][q-1], edges in variable-major order.  For parity tests.

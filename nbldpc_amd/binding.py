@@ -16,13 +16,15 @@ LIB_PATH = os.environ.get("NBL_HIP_LIB") or os.path.join(_HERE, "csrc", "libnbld
 METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
+SOFT_EXTRINSIC = 1
 
 # every symbol include/nbldpc.h declares
 EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
-           "nbl_workspace_bytes", "nbl_decode_batch_bits", "nbl_decode_batch_bits_device", "nbl_soft_output", "nbl_soft_output_device")
+           "nbl_workspace_bytes", "nbl_decode_batch_bits", "nbl_decode_batch_bits_device", "nbl_soft_output", "nbl_soft_output_device",
+           "nbl_decode_batch_samples_prior", "nbl_soft_output_ex", "nbl_soft_output_device_ex", "nbl_decode_batch_samples_idd", "nbl_decode_batch_resident_idd")
 
 
 class NblError(RuntimeError):
@@ -46,6 +48,10 @@ class Params(C.Structure):
 
 class ParamsExt(C.Structure):
     _fields_ = [("bs_nm", C.c_int32), ("bs_nc", C.c_int32), ("bs_factor", C.c_double), ("bs_offset", C.c_double)]
+
+
+class IddParams(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("soft_metric", C.c_int32)]
 
 
 class OsdParams(C.Structure):
@@ -102,6 +108,16 @@ def load_library():
         L.nbl_soft_output.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.nbl_soft_output_device.restype = C.c_int
         L.nbl_soft_output_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_soft_output_ex.restype = C.c_int
+        L.nbl_soft_output_ex.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.nbl_soft_output_device_ex.restype = C.c_int
+        L.nbl_soft_output_device_ex.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_samples_prior.restype = C.c_int
+        L.nbl_decode_batch_samples_prior.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_samples_idd.restype = C.c_int
+        L.nbl_decode_batch_samples_idd.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.POINTER(IddParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_resident_idd.restype = C.c_int
+        L.nbl_decode_batch_resident_idd.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(IddParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_read_state.restype = C.c_int
         L.nbl_read_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_set_record_state.argtypes = [C.c_void_p, C.c_int32]
@@ -277,21 +293,29 @@ class Decoder:
         """Raw device pointers (ints); asynchronous on `stream` (a hipStream_t as int, None = decoder stream)."""
         self._chk(self.lib.nbl_decode_batch_bits_device(self.h, d_bit_llr, B, d_out, d_conv, d_iters, stream))
 
-    def soft_output(self, metric="maxlog", sym=True, bits=True, B=None):
+    def soft_output(self, metric="maxlog", sym=True, bits=True, B=None, extrinsic=False):
         """A-posteriori LLRs of the last decode call (nbl_soft_output): (sym_llr [B][N][q-1] | None, bit_llr [B][N p] | None).
         metric: "maxlog" / "logsum" or SOFT_MAXLOG / SOFT_LOGSUM.  B: the batch of that call; needed only when the call did not go
-        through this object's decode methods (the device forms)."""
+        through this object's decode methods (the device forms).  extrinsic: False = nbl_soft_output; anything else goes through
+        nbl_soft_output_ex with flags = int(extrinsic), so True = SOFT_EXTRINSIC: the sum of the c2v alone, without the channel term."""
         m = {"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(metric, metric)
         B = max(self._last_B() if B is None else B, 1)       # (before the first decode the call is refused; the buffers only have to exist)
         S = np.zeros((B, self.code.N, self.code.q - 1)) if sym else None
         Lb = np.zeros((B, self.code.N * (self.code.q.bit_length() - 1))) if bits else None
-        self._chk(self.lib.nbl_soft_output(self.h, int(m), S.ctypes.data if sym else None, Lb.ctypes.data if bits else None))
+        if extrinsic is False:
+            self._chk(self.lib.nbl_soft_output(self.h, int(m), S.ctypes.data if sym else None, Lb.ctypes.data if bits else None))
+        else:
+            self._chk(self.lib.nbl_soft_output_ex(self.h, int(m), int(extrinsic), S.ctypes.data if sym else None, Lb.ctypes.data if bits else None))
         return S, Lb
 
-    def soft_output_device(self, metric, d_sym_llr, d_bit_llr, stream=None):
-        """Raw device pointers (ints, None = that output is not wanted); enqueued on `stream`, not synchronised."""
+    def soft_output_device(self, metric, d_sym_llr, d_bit_llr, stream=None, extrinsic=False):
+        """Raw device pointers (ints, None = that output is not wanted); enqueued on `stream`, not synchronised.  extrinsic as in
+        soft_output (nbl_soft_output_device_ex)."""
         m = {"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(metric, metric)
-        self._chk(self.lib.nbl_soft_output_device(self.h, int(m), d_sym_llr, d_bit_llr, stream))
+        if extrinsic is False:
+            self._chk(self.lib.nbl_soft_output_device(self.h, int(m), d_sym_llr, d_bit_llr, stream))
+        else:
+            self._chk(self.lib.nbl_soft_output_device_ex(self.h, int(m), int(extrinsic), d_sym_llr, d_bit_llr, stream))
 
     def _last_B(self):
         """batch size of the last decode call (nbl_debug_last_batch; 0 before the first)"""
@@ -320,16 +344,37 @@ class Decoder:
             self._chk(self.lib.nbl_set_demodulator_ex(self.h, C.byref(d), C.byref(ext)))
         self._dm_src, self._dm_cons = dm_src, dm_cons
 
-    def decode_samples(self, rx, sigma):
-        """rx: [B][L][2] received samples -> (out, converged, iters); L_ch is built on the device."""
+    def decode_samples(self, rx, sigma, prior=None):
+        """rx: [B][L][2] received samples -> (out, converged, iters); L_ch is built on the device.  prior: None, or [B][N p] bit LLRs
+        ln P(1) / P(0) per code bit for the general demodulator (nbl_decode_batch_samples_prior)."""
         rx = np.ascontiguousarray(rx, dtype=np.float64)
         B = rx.shape[0]
         out = np.zeros((B, self.code.N), dtype=np.int32)
         conv = np.zeros(B, dtype=np.uint8)
         iters = np.zeros(B, dtype=np.int32)
+        if prior is not None:
+            prior = np.ascontiguousarray(prior, dtype=np.float64)
+            assert prior.shape == (B, self.code.N * (self.code.q.bit_length() - 1)), prior.shape
+            self._chk(self.lib.nbl_decode_batch_samples_prior(self.h, rx.ctypes.data, prior.ctypes.data, sigma, B, out.ctypes.data, conv.ctypes.data,
+                                                              iters.ctypes.data))
+            return out, conv, iters
         self.lib.nbl_decode_batch_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self.lib.nbl_decode_batch_samples(self.h, rx.ctypes.data, sigma, B, out.ctypes.data, conv.ctypes.data, iters.ctypes.data))
         return out, conv, iters
+
+    def decode_samples_idd(self, rx, sigma, passes, soft="maxlog"):
+        """Iterative demapping (nbl_decode_batch_samples_idd): up to `passes` rounds of prior-aware demodulator + decode per codeword,
+        the prior of a round being the extrinsic bit LLRs (metric `soft`) of the round before -> (out, converged, iters, passes_used)"""
+        rx = np.ascontiguousarray(rx, dtype=np.float64)
+        B = rx.shape[0]
+        out = np.zeros((B, self.code.N), dtype=np.int32)
+        conv = np.zeros(B, dtype=np.uint8)
+        iters = np.zeros(B, dtype=np.int32)
+        used = np.zeros(B, dtype=np.int32)
+        idd = IddParams(int(passes), int({"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(soft, soft)))
+        self._chk(self.lib.nbl_decode_batch_samples_idd(self.h, rx.ctypes.data, sigma, B, C.byref(idd), out.ctypes.data, conv.ctypes.data,
+                                                        iters.ctypes.data, used.ctypes.data))
+        return out, conv, iters, used
 
     def decode_noise(self, tx_index, lane_state, sigma):
         """tx_index [B][L] uint8, lane_state [B][3] uint32 (CRand state before the frame): channel + demodulator + decode on the device"""
@@ -349,11 +394,19 @@ class Decoder:
         self.lib.nbl_channel_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32]
         self._chk(self.lib.nbl_channel_batch(self.h, slot, tx_index.ctypes.data, lane_state.ctypes.data, sigma, tx_index.shape[0]))
 
-    def decode_resident(self, slot, sigma, B, want_out=True):
-        """want_out=False: out_sym = NULL (legal once a transmitter is set), the first element returned is None"""
+    def decode_resident(self, slot, sigma, B, want_out=True, passes=1, soft="maxlog"):
+        """want_out=False: out_sym = NULL (legal once a transmitter is set), the first element returned is None.  passes=1 (an int):
+        nbl_decode_batch_resident, three values; anything else goes through nbl_decode_batch_resident_idd and a fourth value,
+        passes_used, is returned"""
         out = np.zeros((B, self.code.N), dtype=np.int32) if want_out else None
         conv = np.zeros(B, dtype=np.uint8)
         iters = np.zeros(B, dtype=np.int32)
+        if passes != 1:
+            used = np.zeros(B, dtype=np.int32)
+            idd = IddParams(int(passes), int({"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(soft, soft)))
+            self._chk(self.lib.nbl_decode_batch_resident_idd(self.h, slot, sigma, B, C.byref(idd), out.ctypes.data if want_out else None,
+                                                             conv.ctypes.data, iters.ctypes.data, used.ctypes.data))
+            return out, conv, iters, used
         self.lib.nbl_decode_batch_resident.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self.lib.nbl_decode_batch_resident(self.h, slot, sigma, B, out.ctypes.data if want_out else None, conv.ctypes.data, iters.ctypes.data))
         return out, conv, iters

@@ -60,6 +60,19 @@ struct nbl_decoder {
 	NblDemodPoint *d_dmdesc = nullptr; // [N][p + 1]
 	double *d_rx = nullptr;
 	size_t d_rx_cap = 0;
+	// iterative demapping (nbl_decode_batch_samples_prior / _idd)
+	int *d_tinv = nullptr;             // [L m] general path: the code bit that claims label bit t (the inverse of src), -1 = nobody
+	double *d_prior = nullptr;         // staging of a host prior [B][N p]
+	size_t d_prior_cap = 0;
+	struct Idd {                       // buffers of the loop, grown on demand, counted in soft_bytes
+		double *rx[2] = {nullptr, nullptr};  // samples of the survivors, ping-pong (pass k reads one, the gather fills the other)
+		int *idx[2] = {nullptr, nullptr};    // their batch positions
+		double *ext = nullptr, *prior = nullptr; // extrinsic bit LLRs of a pass [n][N p]; the survivors' rows of it = the next prior
+		int *res_out = nullptr, *res_iters = nullptr, *res_pass = nullptr; // [B][N], [B], [B]: results at batch positions
+		uint8_t *res_done = nullptr;
+		size_t rx_cap[2] = {0, 0}, idx_cap[2] = {0, 0}, ext_cap = 0, prior_cap = 0, out_cap = 0, iters_cap = 0, pass_cap = 0, done_cap = 0;
+	} idd;
+	bool idd_sub = false;              // the last decode call was a loop with passes > 1: the workspace holds its last sub-batch
 	// bit-LLR input and soft output (nbl_decode_batch_bits, nbl_soft_output): staging of the host forms, grown on demand
 	double *d_lam = nullptr, *d_soft_sym = nullptr, *d_soft_bit = nullptr;
 	size_t d_lam_cap = 0, d_soft_sym_cap = 0, d_soft_bit_cap = 0;
@@ -770,6 +783,9 @@ extern "C" void nbl_destroy(nbl_decoder *d)
 	if (d->d_cons) (void)hipFree(d->d_cons);
 	if (d->d_dmdesc) (void)hipFree(d->d_dmdesc);
 	if (d->d_rx) (void)hipFree(d->d_rx);
+	for (void *p : {(void *)d->d_tinv, (void *)d->d_prior, (void *)d->idd.rx[0], (void *)d->idd.rx[1], (void *)d->idd.idx[0], (void *)d->idd.idx[1],
+	                (void *)d->idd.ext, (void *)d->idd.prior, (void *)d->idd.res_out, (void *)d->idd.res_iters, (void *)d->idd.res_pass, (void *)d->idd.res_done})
+		if (p) (void)hipFree(p);
 	for (double *p : {d->d_lam, d->d_soft_sym, d->d_soft_bit})
 		if (p) (void)hipFree(p);
 	for (double *p : d->d_rxs)
@@ -1008,6 +1024,7 @@ static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hip
 	const nbl_params &p = d->prm;
 	IterCtx c;
 	c.d = d;
+	d->idd_sub = false; // (the loop sets it again after its last pass)
 	c.damp = p.method != NBL_METHOD_EMS;
 	NblRun &r = c.r;
 	r = NblRun{};
@@ -1131,7 +1148,7 @@ extern "C" nbl_status nbl_decode_batch(nbl_decoder *d, const double *L_ch, int32
 
 // The per-symbol descriptor of the general demodulator (nbl_common.h, NblDemodPoint) from src [N p]; every index is checked here,
 // before anything is indexed by it.
-static nbl_status build_demod_desc(nbl_decoder *d, const nbl_demod_desc *dm, int m, std::vector<NblDemodPoint> &desc)
+static nbl_status build_demod_desc(nbl_decoder *d, const nbl_demod_desc *dm, int m, std::vector<NblDemodPoint> &desc, std::vector<int> &tinv)
 {
 	const int N = d->g.N, p = d->g.p;
 	const long long T = (long long)dm->n_mod_sym * m;
@@ -1143,6 +1160,9 @@ static nbl_status build_demod_desc(nbl_decoder *d, const nbl_demod_desc *dm, int
 		if (seen[t]) { d->err = "demodulator source: label bit " + std::to_string(t) + " is claimed twice"; return NBL_ERR_ARG; }
 		seen[t] = 1;
 	}
+	tinv.assign((size_t)T, -1); // the inverse of src, for the prior-aware kernel: who claims label bit t
+	for (size_t i = 0; i < (size_t)N * p; i++)
+		if (dm->src[i] >= 0) tinv[dm->src[i]] = (int)i;
 	NblDemodPoint none{};
 	none.s = 0; none.nown = 0;
 	for (int i = 0; i < 8; i++) none.own[i] = -1;
@@ -1198,8 +1218,9 @@ extern "C" nbl_status nbl_set_demodulator_ex(nbl_decoder *d, const nbl_demod_des
 	const int m = ilog2(M);
 	const size_t nsrc = (general || M == 2) ? (size_t)N * p : (size_t)N;
 	std::vector<NblDemodPoint> desc;
+	std::vector<int> tinv;
 	if (general) {
-		const nbl_status s = build_demod_desc(d, dm, m, desc);
+		const nbl_status s = build_demod_desc(d, dm, m, desc, tinv);
 		if (s) return s;
 	} else {
 		for (size_t i = 0; i < nsrc; i++)
@@ -1212,10 +1233,13 @@ extern "C" nbl_status nbl_set_demodulator_ex(nbl_decoder *d, const nbl_demod_des
 	if (d->d_src) (void)hipFree(d->d_src);
 	if (d->d_cons) (void)hipFree(d->d_cons);
 	if (d->d_dmdesc) (void)hipFree(d->d_dmdesc);
-	d->d_src = nullptr; d->d_cons = nullptr; d->d_dmdesc = nullptr;
+	if (d->d_tinv) (void)hipFree(d->d_tinv);
+	d->d_src = nullptr; d->d_cons = nullptr; d->d_dmdesc = nullptr; d->d_tinv = nullptr;
 	if (general) {
 		HIP_TRY(d, hipMalloc((void **)&d->d_dmdesc, desc.size() * sizeof(NblDemodPoint)));
 		HIP_TRY(d, hipMemcpy(d->d_dmdesc, desc.data(), desc.size() * sizeof(NblDemodPoint), hipMemcpyHostToDevice));
+		HIP_TRY(d, hipMalloc((void **)&d->d_tinv, tinv.size() * sizeof(int)));
+		HIP_TRY(d, hipMemcpy(d->d_tinv, tinv.data(), tinv.size() * sizeof(int), hipMemcpyHostToDevice));
 	} else {
 		HIP_TRY(d, hipMalloc((void **)&d->d_src, nsrc * 4));
 		HIP_TRY(d, hipMemcpy(d->d_src, dm->src, nsrc * 4, hipMemcpyHostToDevice));
@@ -1240,16 +1264,36 @@ extern "C" nbl_status nbl_set_demodulator_ex(nbl_decoder *d, const nbl_demod_des
 extern "C" nbl_status nbl_set_demodulator(nbl_decoder *d, const nbl_demod_desc *dm) { return nbl_set_demodulator_ex(d, dm, nullptr); }
 
 // received samples -> L_ch in the workspace: the BPSK / q-ary kernel, or the general one where nbl_set_demodulator_ex chose it
-static hipError_t launch_demod(nbl_decoder *d, const double *d_rx, double sigma, int B)
+// d_prior [B][N p] (may be NULL): the prior-aware instance of the general kernel; the BPSK / q-ary kernels have no foreign position, a
+// prior is inert there
+static hipError_t launch_demod(nbl_decoder *d, const double *d_rx, double sigma, int B, const double *d_prior = nullptr)
 {
-	if (d->dm_general) return nbl_launch_demod_general(d_rx, d->dm_L, sigma, d->dm_order, d->dm_metric, d->d_cons, d->d_dmdesc, d->g, d->w, B, d->stream);
+	if (d->dm_general) return nbl_launch_demod_general(d_rx, d->dm_L, sigma, d->dm_order, d->dm_metric, d->d_cons, d->d_dmdesc, d->g, d->w, B, d->stream, d_prior, d->d_tinv);
 	return nbl_launch_demod(d_rx, d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream);
 }
 
 static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_t st);
 
-extern "C" nbl_status nbl_decode_batch_samples(nbl_decoder *d, const double *rx, double sigma, int32_t B, int32_t *out_sym,
-                                               uint8_t *converged, int32_t *iters)
+template <typename T> static nbl_status grow_staging(nbl_decoder *d, T **buf, size_t *cap, size_t bytes);
+
+// host samples [B][L][2] -> d_rx (grown on demand), on the decoder's stream
+static nbl_status stage_rx(nbl_decoder *d, const double *rx, int B)
+{
+	const size_t bytes = (size_t)B * d->dm_L * 16;
+	if (bytes > d->d_rx_cap) {
+		if (d->d_rx) (void)hipFree(d->d_rx);
+		d->d_rx = nullptr;
+		d->d_rx_cap = 0;
+		HIP_TRY(d, hipMalloc((void **)&d->d_rx, bytes));
+		d->d_rx_cap = bytes;
+	}
+	HIP_TRY(d, hipMemcpyAsync(d->d_rx, rx, bytes, hipMemcpyHostToDevice, d->stream));
+	return NBL_OK;
+}
+
+// nbl_decode_batch_samples, and with a prior nbl_decode_batch_samples_prior
+static nbl_status decode_samples(nbl_decoder *d, const double *rx, const double *prior, double sigma, int32_t B, int32_t *out_sym,
+                                 uint8_t *converged, int32_t *iters)
 {
 	if (!d || !rx || !out_sym || B < 0 || !(sigma > 0)) return NBL_ERR_ARG;
 	if (!d->dm_order) { d->err = "nbl_set_demodulator has not been called"; return NBL_ERR_ARG; }
@@ -1258,15 +1302,15 @@ extern "C" nbl_status nbl_decode_batch_samples(nbl_decoder *d, const double *rx,
 	HIP_TRY(d, hipSetDevice(d->device));
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
-	const size_t bytes = (size_t)B * d->dm_L * 16;
-	if (bytes > d->d_rx_cap) {
-		if (d->d_rx) (void)hipFree(d->d_rx);
-		d->d_rx = nullptr;
-		HIP_TRY(d, hipMalloc((void **)&d->d_rx, bytes));
-		d->d_rx_cap = bytes;
+	if ((s = stage_rx(d, rx, B))) return s;
+	if (prior && d->dm_general) {
+		const size_t pbytes = (size_t)B * d->g.N * d->g.p * 8;
+		if ((s = grow_staging(d, &d->d_prior, &d->d_prior_cap, pbytes))) return s;
+		HIP_TRY(d, hipMemcpyAsync(d->d_prior, prior, pbytes, hipMemcpyHostToDevice, d->stream));
+		HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B, d->d_prior));
+	} else {
+		HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B));
 	}
-	HIP_TRY(d, hipMemcpyAsync(d->d_rx, rx, bytes, hipMemcpyHostToDevice, d->stream));
-	HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B));
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
 	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->w.done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
@@ -1275,10 +1319,22 @@ extern "C" nbl_status nbl_decode_batch_samples(nbl_decoder *d, const double *rx,
 	return NBL_OK;
 }
 
+extern "C" nbl_status nbl_decode_batch_samples(nbl_decoder *d, const double *rx, double sigma, int32_t B, int32_t *out_sym,
+                                               uint8_t *converged, int32_t *iters)
+{
+	return decode_samples(d, rx, nullptr, sigma, B, out_sym, converged, iters);
+}
+
+extern "C" nbl_status nbl_decode_batch_samples_prior(nbl_decoder *d, const double *rx, const double *prior, double sigma, int32_t B,
+                                                     int32_t *out_sym, uint8_t *converged, int32_t *iters)
+{
+	return decode_samples(d, rx, prior, sigma, B, out_sym, converged, iters);
+}
+
 // ---- bit-LLR input and batched soft output (nbl_soft.hip) ------------------------------------------------
 
 // a staging buffer grown on demand, like d_rx; counted in nbl_workspace_bytes from the moment it exists
-static nbl_status grow_staging(nbl_decoder *d, double **buf, size_t *cap, size_t bytes)
+template <typename T> static nbl_status grow_staging(nbl_decoder *d, T **buf, size_t *cap, size_t bytes)
 {
 	if (bytes <= *cap) return NBL_OK;
 	if (*buf) (void)hipFree(*buf);
@@ -1334,7 +1390,10 @@ extern "C" nbl_status nbl_decode_batch_bits(nbl_decoder *d, const double *bit_ll
 extern "C" int32_t nbl_debug_last_batch(const nbl_decoder *d) { return d ? d->last_B : 0; }
 
 // what nbl_soft_output refuses, before the device is touched
-static nbl_status soft_check(nbl_decoder *d, int32_t metric, const double *sym_llr, const double *bit_llr)
+static const char *const IDD_SUB_TEXT = ": the last decode call was an iterative-demapping loop (passes > 1), the workspace holds the "
+                                        "sub-batch of its last pass and not the batch; run an ordinary decode call first";
+
+static nbl_status soft_check(nbl_decoder *d, int32_t metric, uint32_t flags, const double *sym_llr, const double *bit_llr)
 {
 	if (!d) return NBL_ERR_ARG;
 	if (d->prm.method == NBL_METHOD_OSD) { d->err = "nbl_soft_output: an OSD-only decoder (method 6) runs no iterations: there are no messages to form a posterior from"; return NBL_ERR_UNSUPPORTED; }
@@ -1343,7 +1402,14 @@ static nbl_status soft_check(nbl_decoder *d, int32_t metric, const double *sym_l
 		d->err = "nbl_soft_output: unknown metric " + std::to_string(metric) + " (NBL_SOFT_LOGSUM = 0, NBL_SOFT_MAXLOG = 1)";
 		return NBL_ERR_ARG;
 	}
+	if (flags & ~(uint32_t)NBL_SOFT_EXTRINSIC) {
+		char hex[16];
+		snprintf(hex, sizeof hex, "0x%x", (unsigned)(flags & ~(uint32_t)NBL_SOFT_EXTRINSIC));
+		d->err = std::string("nbl_soft_output_ex: unknown flag bits ") + hex + " (NBL_SOFT_EXTRINSIC = 1)";
+		return NBL_ERR_ARG;
+	}
 	if (d->last_B <= 0 || !d->w.Lch) { d->err = "nbl_soft_output: no decode call has run on this handle yet"; return NBL_ERR_ARG; }
+	if (d->idd_sub) { d->err = std::string("nbl_soft_output") + IDD_SUB_TEXT; return NBL_ERR_ARG; }
 	return NBL_OK;
 }
 
@@ -1363,20 +1429,25 @@ static NblSoftSrc soft_src(const nbl_decoder *d)
 	return s;
 }
 
-extern "C" nbl_status nbl_soft_output_device(nbl_decoder *d, int32_t metric, double *d_sym_llr, double *d_bit_llr, void *stream)
+extern "C" nbl_status nbl_soft_output_device_ex(nbl_decoder *d, int32_t metric, uint32_t flags, double *d_sym_llr, double *d_bit_llr, void *stream)
 {
-	nbl_status s = soft_check(d, metric, d_sym_llr, d_bit_llr);
+	nbl_status s = soft_check(d, metric, flags, d_sym_llr, d_bit_llr);
 	if (s) return s;
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
 	hipStream_t st = stream ? (hipStream_t)stream : d->stream;
-	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, d_sym_llr, d_bit_llr, st));
+	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, d_sym_llr, d_bit_llr, st, (flags & NBL_SOFT_EXTRINSIC) != 0));
 	return NBL_OK;
 }
 
-extern "C" nbl_status nbl_soft_output(nbl_decoder *d, int32_t metric, double *sym_llr, double *bit_llr)
+extern "C" nbl_status nbl_soft_output_device(nbl_decoder *d, int32_t metric, double *d_sym_llr, double *d_bit_llr, void *stream)
 {
-	nbl_status s = soft_check(d, metric, sym_llr, bit_llr);
+	return nbl_soft_output_device_ex(d, metric, 0, d_sym_llr, d_bit_llr, stream);
+}
+
+extern "C" nbl_status nbl_soft_output_ex(nbl_decoder *d, int32_t metric, uint32_t flags, double *sym_llr, double *bit_llr)
+{
+	nbl_status s = soft_check(d, metric, flags, sym_llr, bit_llr);
 	if (s) return s;
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
@@ -1385,9 +1456,110 @@ extern "C" nbl_status nbl_soft_output(nbl_decoder *d, int32_t metric, double *sy
 	if (sym_llr && (s = grow_staging(d, &d->d_soft_sym, &d->d_soft_sym_cap, sym_bytes))) return s;
 	if (bit_llr && (s = grow_staging(d, &d->d_soft_bit, &d->d_soft_bit_cap, bit_bytes))) return s;
 	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, sym_llr ? d->d_soft_sym : nullptr,
-	                                  bit_llr ? d->d_soft_bit : nullptr, d->stream));
+	                                  bit_llr ? d->d_soft_bit : nullptr, d->stream, (flags & NBL_SOFT_EXTRINSIC) != 0));
 	if (sym_llr) HIP_TRY(d, hipMemcpyAsync(sym_llr, d->d_soft_sym, sym_bytes, hipMemcpyDeviceToHost, d->stream));
 	if (bit_llr) HIP_TRY(d, hipMemcpyAsync(bit_llr, d->d_soft_bit, bit_bytes, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_soft_output(nbl_decoder *d, int32_t metric, double *sym_llr, double *bit_llr)
+{
+	return nbl_soft_output_ex(d, metric, 0, sym_llr, bit_llr);
+}
+
+// ---- iterative demapping: the loop between the prior-aware demodulator and the decoder --------------------
+
+// what the two _idd entry points refuse beyond what their plain forms refuse, before the device is touched
+static nbl_status idd_check(nbl_decoder *d, const char *who, const nbl_idd_params *idd)
+{
+	const std::string w(who);
+	if (!idd) { d->err = w + ": idd is NULL"; return NBL_ERR_ARG; }
+	if (idd->passes < 1) { d->err = w + ": passes must be at least 1, got " + std::to_string(idd->passes); return NBL_ERR_ARG; }
+	if (idd->soft_metric != NBL_SOFT_LOGSUM && idd->soft_metric != NBL_SOFT_MAXLOG) {
+		d->err = w + ": unknown soft_metric " + std::to_string(idd->soft_metric) + " (NBL_SOFT_LOGSUM = 0, NBL_SOFT_MAXLOG = 1)";
+		return NBL_ERR_ARG;
+	}
+	if (!d->dm_order) { d->err = w + ": nbl_set_demodulator has not been called"; return NBL_ERR_ARG; }
+	if (idd->passes > 1 && d->prm.method == NBL_METHOD_OSD) {
+		d->err = w + ": an OSD-only decoder (method 6) runs no iterations: there are no messages to form a prior from, passes must be 1";
+		return NBL_ERR_UNSUPPORTED;
+	}
+	return NBL_OK;
+}
+
+// passes 1 .. idd->passes over the samples d_rx0 [B][L][2] (only ever read); leaves out / converged / iters / pass of every codeword at
+// its batch position in d->idd.res_*.  One stream synchronisation per pass that has a successor: the survivor count sizes the next grids.
+static nbl_status run_idd(nbl_decoder *d, const double *d_rx0, double sigma, int B, const nbl_idd_params *idd)
+{
+	nbl_decoder::Idd &x = d->idd;
+	const int N = d->g.N, Np = d->g.N * d->g.p, rx_row = 2 * d->dm_L;
+	nbl_status s;
+	if ((s = grow_staging(d, &x.res_out, &x.out_cap, (size_t)B * N * 4))) return s;
+	if ((s = grow_staging(d, &x.res_iters, &x.iters_cap, (size_t)B * 4))) return s;
+	if ((s = grow_staging(d, &x.res_pass, &x.pass_cap, (size_t)B * 4))) return s;
+	if ((s = grow_staging(d, &x.res_done, &x.done_cap, (size_t)B))) return s;
+	const double *rx = d_rx0, *prior = nullptr;
+	const int *idx = nullptr;
+	int n = B, side = 0;
+	for (int k = 1;; k++) {
+		HIP_TRY(d, launch_demod(d, rx, sigma, n, prior));
+		if ((s = run_iterations(d, nullptr, n, d->stream))) return s;
+		HIP_TRY(d, nbl_launch_idd_scatter(d->w.out, d->w.done, d->w.iters, idx, n, N, k, x.res_out, x.res_done, x.res_iters, x.res_pass, d->stream));
+		if (k == idd->passes) break;
+		int live = 0;
+		HIP_TRY(d, nbl_launch_compact(d->w.done, n, d->d_active, (int *)d->w.n_act, d->stream));
+		HIP_TRY(d, hipMemcpyAsync(&live, d->w.n_act, sizeof live, hipMemcpyDeviceToHost, d->stream));
+		HIP_TRY(d, hipStreamSynchronize(d->stream));
+		if (live <= 0) break;
+		if (live > n) { d->err = "iterative demapping: the active list is longer than the batch"; return NBL_ERR_HIP; }
+		if ((s = grow_staging(d, &x.ext, &x.ext_cap, (size_t)n * Np * 8))) return s;
+		if ((s = grow_staging(d, &x.prior, &x.prior_cap, (size_t)live * Np * 8))) return s;
+		if ((s = grow_staging(d, &x.rx[side], &x.rx_cap[side], (size_t)live * rx_row * 8))) return s;
+		if ((s = grow_staging(d, &x.idx[side], &x.idx_cap[side], (size_t)live * 4))) return s;
+		HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), n, idd->soft_metric, nullptr, x.ext, d->stream, true));
+		HIP_TRY(d, nbl_launch_idd_gather(d->d_active, live, rx, rx_row, x.ext, Np, idx, x.rx[side], x.prior, x.idx[side], d->stream));
+		rx = x.rx[side];
+		idx = x.idx[side];
+		prior = x.prior;
+		side ^= 1;
+		n = live;
+	}
+	d->idd_sub = true;
+	return NBL_OK;
+}
+
+// a demodulator without a foreign position (BPSK / q-ary, not forced general): every pass is the same decode, so pass 1 is run alone
+// and a codeword that did not converge is reported with the pass the definition ends on
+static void idd_inert_passes(const nbl_idd_params *idd, const uint8_t *conv, int32_t B, int32_t *passes_used)
+{
+	if (passes_used)
+		for (int b = 0; b < B; b++) passes_used[b] = conv[b] ? 1 : idd->passes;
+}
+
+extern "C" nbl_status nbl_decode_batch_samples_idd(nbl_decoder *d, const double *rx, double sigma, int32_t B, const nbl_idd_params *idd,
+                                                   int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used)
+{
+	if (!d || !rx || !out_sym || B < 0 || !(sigma > 0)) return NBL_ERR_ARG;
+	nbl_status s = idd_check(d, "nbl_decode_batch_samples_idd", idd);
+	if (s) return s;
+	if (B == 0) return NBL_OK;
+	if (idd->passes == 1 || !d->dm_general) {
+		std::vector<uint8_t> conv(converged ? 0 : (size_t)B);
+		uint8_t *cv = converged ? converged : conv.data();
+		if ((s = decode_samples(d, rx, nullptr, sigma, B, out_sym, cv, iters))) return s;
+		idd_inert_passes(idd, cv, B, passes_used);
+		return NBL_OK;
+	}
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	if ((s = ensure_workspace(d, B))) return s;
+	if ((s = stage_rx(d, rx, B))) return s;
+	if ((s = run_idd(d, d->d_rx, sigma, B, idd))) return s;
+	HIP_TRY(d, hipMemcpyAsync(out_sym, d->idd.res_out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
+	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->idd.res_done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
+	if (iters) HIP_TRY(d, hipMemcpyAsync(iters, d->idd.res_iters, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+	if (passes_used) HIP_TRY(d, hipMemcpyAsync(passes_used, d->idd.res_pass, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(d, hipStreamSynchronize(d->stream));
 	return NBL_OK;
 }
@@ -1576,11 +1748,18 @@ static nbl_status ensure_slot_dec(nbl_decoder *d, int slot, int B)
 	return NBL_OK;
 }
 
+// what the two resident decode calls refuse about their slot and outputs
+static nbl_status resident_check(nbl_decoder *d, int slot, int B, const int32_t *out_sym)
+{
+	if (!out_sym && !d->tx.on) { d->err = "nbl_decode_batch_resident: out_sym may only be NULL once nbl_set_transmitter has been called"; return NBL_ERR_ARG; }
+	if (d->rxs_B[slot] != B) { d->err = "nbl_decode_batch_resident: slot does not hold the samples of a batch of this size (nbl_channel_batch first)"; return NBL_ERR_ARG; }
+	return NBL_OK;
+}
+
 extern "C" nbl_status nbl_decode_batch_resident(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t *out_sym, uint8_t *converged, int32_t *iters)
 {
 	if (!d || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0)) return NBL_ERR_ARG;
-	if (!out_sym && !d->tx.on) { d->err = "nbl_decode_batch_resident: out_sym may only be NULL once nbl_set_transmitter has been called"; return NBL_ERR_ARG; }
-	if (d->rxs_B[slot] != B) { d->err = "nbl_decode_batch_resident: slot does not hold the samples of a batch of this size (nbl_channel_batch first)"; return NBL_ERR_ARG; }
+	if (nbl_status rs = resident_check(d, slot, B, out_sym)) return rs;
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
 	nbl_status s = ensure_workspace(d, B);
@@ -1597,6 +1776,71 @@ extern "C" nbl_status nbl_decode_batch_resident(nbl_decoder *d, int32_t slot, do
 	if (iters) HIP_TRY(d, hipMemcpyAsync(iters, d->w.iters, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(d, hipStreamSynchronize(d->stream));
 	if (d->tx.on) d->tx.dec_B[slot] = B;
+	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_decode_batch_resident_idd(nbl_decoder *d, int32_t slot, double sigma, int32_t B, const nbl_idd_params *idd,
+                                                    int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used)
+{
+	if (!d || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0)) return NBL_ERR_ARG;
+	nbl_status s = idd_check(d, "nbl_decode_batch_resident_idd", idd);
+	if (s) return s;
+	if (idd->passes == 1 || !d->dm_general) {
+		std::vector<uint8_t> conv(converged ? 0 : (size_t)B);
+		uint8_t *cv = converged ? converged : conv.data();
+		if ((s = nbl_decode_batch_resident(d, slot, sigma, B, out_sym, cv, iters))) return s;
+		idd_inert_passes(idd, cv, B, passes_used);
+		return NBL_OK;
+	}
+	if (nbl_status rs = resident_check(d, slot, B, out_sym)) return rs;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	if ((s = ensure_workspace(d, B))) return s;
+	if (d->tx.on) d->tx.dec_B[slot] = 0;
+	if ((s = run_idd(d, d->d_rxs[slot], sigma, B, idd))) return s; // (the slot's samples are only read)
+	if (out_sym) HIP_TRY(d, hipMemcpyAsync(out_sym, d->idd.res_out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
+	if (d->tx.on) { // the slot keeps the final words for nbl_count_errors
+		if ((s = ensure_slot_dec(d, slot, B))) return s;
+		HIP_TRY(d, hipMemcpyAsync(d->tx.dec[slot], d->idd.res_out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToDevice, d->stream));
+	}
+	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->idd.res_done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
+	if (iters) HIP_TRY(d, hipMemcpyAsync(iters, d->idd.res_iters, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+	if (passes_used) HIP_TRY(d, hipMemcpyAsync(passes_used, d->idd.res_pass, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+	HIP_TRY(d, hipStreamSynchronize(d->stream));
+	if (d->tx.on) d->tx.dec_B[slot] = B;
+	return NBL_OK;
+}
+
+// Diagnostic only (not part of include/nbldpc.h): device time in milliseconds of ONE launch of the demodulator on the samples a slot
+// holds, between two events on the decoder's stream -- with_prior != 0: the prior-aware instance, on an all-zero prior (the kernel's
+// work does not depend on the values).  For tools/idd_pass.py.
+extern "C" nbl_status nbl_debug_time_demod(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t with_prior, double *ms)
+{
+	if (!d || !ms || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0) || !d->dm_order || d->rxs_B[slot] != B) return NBL_ERR_ARG;
+	d->err.clear();
+	HIP_TRY(d, hipSetDevice(d->device));
+	nbl_status s = ensure_workspace(d, B);
+	if (s) return s;
+	const double *prior = nullptr;
+	if (with_prior && d->dm_general) {
+		const size_t pbytes = (size_t)B * d->g.N * d->g.p * 8;
+		if ((s = grow_staging(d, &d->d_prior, &d->d_prior_cap, pbytes))) return s;
+		HIP_TRY(d, hipMemsetAsync(d->d_prior, 0, pbytes, d->stream));
+		prior = d->d_prior;
+	}
+	hipEvent_t a = nullptr, b = nullptr;
+	HIP_TRY(d, hipEventCreate(&a));
+	HIP_TRY(d, hipEventCreate(&b));
+	hipError_t e = hipEventRecord(a, d->stream);
+	if (e == hipSuccess) e = launch_demod(d, d->d_rxs[slot], sigma, B, prior);
+	if (e == hipSuccess) e = hipEventRecord(b, d->stream);
+	if (e == hipSuccess) e = hipEventSynchronize(b);
+	float t = 0;
+	if (e == hipSuccess) e = hipEventElapsedTime(&t, a, b);
+	(void)hipEventDestroy(a);
+	(void)hipEventDestroy(b);
+	HIP_TRY(d, e);
+	*ms = t;
 	return NBL_OK;
 }
 
@@ -1634,7 +1878,9 @@ extern "C" nbl_status nbl_debug_read_lch(nbl_decoder *d, int32_t b, double *out)
 
 extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, double *v2c, double *c2v)
 {
-	if (!d || b < 0 || b >= d->last_B) return NBL_ERR_ARG;
+	if (!d) return NBL_ERR_ARG;
+	if (d->idd_sub) { d->err = std::string("nbl_read_state") + IDD_SUB_TEXT; return NBL_ERR_ARG; }
+	if (b < 0 || b >= d->last_B) return NBL_ERR_ARG;
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
 	const int q = d->g.q, N = d->g.N, E = d->g.E;

@@ -9,6 +9,12 @@
 //   4. every lane adds (tab[0] - tab[pattern of a]) / (2 sigma^2) to its q / 64 values of a, held in registers
 // The own pattern lists the own label positions in ascending position i, bit r = the r-th of them.  LDS per wave: M + 2^own <= 512
 // doubles.  Every expression keeps the order the header defines; the library is compiled with -ffp-contract=off.
+//
+// PRIOR (nbl_decode_batch_samples_prior, the passes of nbl_decode_batch_samples_idd): between steps 1 and 2 lane c
+// takes  (2 sigma^2) * (the priors of the claimed foreign label bits that are 1 in c, added in ascending position)  off its distance.
+// The at most m prior values of a point are the same for the whole wave: codeword, point and the claim table tinv[s m + i] are made
+// provably uniform, so they arrive as scalar loads, not as 64 lanes reading one address.  The instance without PRIOR is the kernel
+// the prior-less calls have always launched.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/nbldpc.h"
@@ -47,9 +53,11 @@ __device__ __forceinline__ int demod_pattern_of_value(const NblDemodPoint &pt, i
 	return pat;
 }
 
+template <bool PRIOR>
 __global__ __launch_bounds__(256) void demod_general_kernel(const double *__restrict__ rx, int L, double sigma_n, int M, int m, int metric,
                                                             const double *__restrict__ cons, const NblDemodPoint *__restrict__ desc,
-                                                            NblGraphDev g, NblWork w, int B)
+                                                            NblGraphDev g, NblWork w, int B, const double *__restrict__ prior,
+                                                            const int *__restrict__ tinv)
 {
 	__shared__ double lds[4][512];
 	const int lane = lane_id();
@@ -68,10 +76,36 @@ __global__ __launch_bounds__(256) void demod_general_kernel(const double *__rest
 		const NblDemodPoint pt = dn[1 + k];
 		const double re = r[2 * pt.s], im = r[2 * pt.s + 1];
 		const int npat = 1 << pt.nown, nfor = 1 << (m - pt.nown);
+		// PRIOR: pv[i] = prior of the code bit that claims foreign label position i of this point, cm bit i = there is one
+		double pv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+		int cm = 0;
+		if constexpr (PRIOR) {
+			int fm = 0;
+#pragma unroll
+			for (int i = 0; i < 8; i++)
+				if (i < m && pt.own[i] < 0) fm |= 1 << i;
+			fm = uniform(fm);
+			const int *ti = tinv + (size_t)uniform(pt.s) * m;
+			const double *pr = prior + (size_t)uniform(b) * g.N * p;
+#pragma unroll
+			for (int i = 0; i < 8; i++)
+				if ((fm >> i) & 1) {
+					const int gb = ti[i];
+					if (gb >= 0) { pv[i] = pr[gb]; cm |= 1 << i; }
+				}
+		}
 		DSYNC(); // the previous point's table has been read by every lane
 		for (int c = lane; c < M; c += 64) {
 			const double cr = cons[2 * c], ci = cons[2 * c + 1];
-			dist[c] = (re - cr) * (re - cr) + (im - ci) * (im - ci);
+			double d = (re - cr) * (re - cr) + (im - ci) * (im - ci);
+			if constexpr (PRIOR) {
+				double A = 0.0;
+#pragma unroll
+				for (int i = 0; i < 8; i++)
+					if (((cm >> i) & 1) && ((c << i >> (m - 1)) & 1)) A = A + pv[i]; // (bit i of the label has weight 2^(m-1-i); cm is 0 from m up)
+				d = d - two * A;
+			}
+			dist[c] = d;
 		}
 		DSYNC();
 		for (int pat = lane; pat < npat; pat += 64) {
@@ -111,13 +145,19 @@ __global__ __launch_bounds__(256) void demod_general_kernel(const double *__rest
 }
 
 hipError_t nbl_launch_demod_general(const double *d_rx, int L, double sigma, int mod_order, int metric, const double *d_cons,
-                                    const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st)
+                                    const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st,
+                                    const double *d_prior, const int *d_tinv)
 {
 	int m = 0;
 	while ((1 << m) < mod_order) m++;
 	if (m < 1 || m > 8 || (1 << m) != mod_order || g.q > 256 || !d_cons || !d_desc) return hipErrorInvalidValue;
 	long long nodes = (long long)B * g.N;
 	dim3 grid((unsigned)((nodes + 3) / 4)), block(256);
-	demod_general_kernel<<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B);
+	if (d_prior) {
+		if (!d_tinv) return hipErrorInvalidValue;
+		demod_general_kernel<true><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, d_prior, d_tinv);
+	} else {
+		demod_general_kernel<false><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, nullptr, nullptr);
+	}
 	return hipGetLastError();
 }

@@ -9,7 +9,8 @@ hipError_t nbl_launch_demod(const double *d_rx, int L, double sigma, int mod_ord
                             const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
 // general demodulator, any mod_order = 2^m <= 256 (nbl_demod.hip); metric: NBL_DEMOD_* of include/nbldpc.h
 hipError_t nbl_launch_demod_general(const double *d_rx, int L, double sigma, int mod_order, int metric, const double *d_cons,
-                                    const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
+                                    const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st,
+                                    const double *d_prior = nullptr /* [B][N p]: the prior-aware instance */, const int *d_tinv = nullptr);
 hipError_t nbl_launch_vn(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool damp, hipStream_t st);
 hipError_t nbl_launch_syn(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_compact(const uint8_t *done, int B, int *active, int *n_act, hipStream_t st);
@@ -69,7 +70,13 @@ hipError_t nbl_launch_cn_bp64(const NblGraphDev &g, const NblWork &w, const NblR
 // may be NULL)
 hipError_t nbl_launch_bits_to_lch(const double *d_lam, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
 hipError_t nbl_launch_soft_output(const NblGraphDev &g, const double *d_Lch, const NblSoftSrc &src, int B, int metric, double *d_sym_llr,
-                                  double *d_bit_llr, hipStream_t st);
+                                  double *d_bit_llr, hipStream_t st, bool extrinsic = false /* NBL_SOFT_EXTRINSIC: P starts from 0.0 */);
+// iterative demapping (nbl_idd.hip): results of a pass to the batch positions of its codewords; the survivors' rows to dense buffers
+hipError_t nbl_launch_idd_scatter(const int *d_out, const uint8_t *d_done, const int *d_iters, const int *d_idx /* NULL: the identity */,
+                                  int n, int N, int pass, int *d_res_out, uint8_t *d_res_done, int *d_res_iters, int *d_res_pass, hipStream_t st);
+hipError_t nbl_launch_idd_gather(const int *d_active, int n, const double *d_rx_src, int rx_row, const double *d_ext_src, int prior_row,
+                                 const int *d_idx_src /* NULL: the identity */, double *d_rx_dst, double *d_prior_dst, int *d_idx_dst,
+                                 hipStream_t st);
 
 // AWGN channel + CRand on the device (nbl_noise.hip)
 hipError_t nbl_launch_noise_gen(const uint32_t *state, const uint32_t *jump, int L, int B, double *fn, uint32_t *flag_idx, double *flag_arg,

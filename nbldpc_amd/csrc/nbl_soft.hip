@@ -4,7 +4,8 @@
 //   bits_to_lch_kernel   per-bit LLRs [B][N p] -> the padded L_ch [B][N][q] of the workspace: the reference's RX_LLR_BIT -> RX_LLR_SYM
 //                        loop (Comm.cpp:359-373), accumulated from 0.0 in ascending bit order
 //   soft_output_kernel   the a-posteriori vector P[n] = L_ch[n] + c2v of n's edges (vn_decide_kernel's loads and sums, the same order) of
-//                        the LAST decode call, written out unpadded, and its p bit marginals (max-log, or log-sum-exp)
+//                        the LAST decode call, written out unpadded, and its p bit marginals (max-log, or log-sum-exp); the EXT
+//                        instances (NBL_SOFT_EXTRINSIC) start P[n] from 0.0 and never load L_ch
 //
 // The soft-output pass is one wave per (codeword, variable) at EVERY q, also where q < 64 leaves lanes idle.  That is deliberate: the
 // pass runs once per decode call, not once per iteration, its cost is the one read of L_ch and c2v either way, and one variable per wave
@@ -66,7 +67,7 @@ __device__ __forceinline__ double wave_sum(double v)
 	return v;
 }
 
-template <int Q>
+template <int Q, bool EXT = false>
 __global__ __launch_bounds__(256) void soft_output_kernel(NblGraphDev g, const double *__restrict__ Lch, NblSoftSrc s, int B, int metric,
                                                           double *__restrict__ sym_llr, double *__restrict__ bit_llr)
 {
@@ -92,7 +93,8 @@ __global__ __launch_bounds__(256) void soft_output_kernel(NblGraphDev g, const d
 #pragma unroll
 	for (int i = 0; i < NS; i++) {
 		const int a = lane + 64 * i;
-		post[i] = (a < Q) ? L[a] : 0.0;
+		if constexpr (EXT) post[i] = 0.0;
+		else post[i] = (a < Q) ? L[a] : 0.0;
 	}
 	for (int d = 0; d < dv; d++) {
 		const double *Cd = C + (size_t)g.v_cpos[e0 + d] * Q;
@@ -163,11 +165,15 @@ __global__ __launch_bounds__(256) void soft_output_kernel(NblGraphDev g, const d
 	}
 
 hipError_t nbl_launch_soft_output(const NblGraphDev &g, const double *d_Lch, const NblSoftSrc &src, int B, int metric, double *d_sym_llr,
-                                  double *d_bit_llr, hipStream_t st)
+                                  double *d_bit_llr, hipStream_t st, bool extrinsic)
 {
 	const long long nodes = (long long)B * g.N, blocks = (nodes + 3) / 4;
 	if (B < 1 || blocks > 0x7fffffffLL || !src.last || (src.per_codeword && (!src.bufA || !src.bufB || !src.done || !src.iters))) return hipErrorInvalidValue;
 	dim3 grid((unsigned)blocks), block(256);
-	NBL_SOFT_Q(g.q, soft_output_kernel<QQ><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
+	if (extrinsic) {
+		NBL_SOFT_Q(g.q, soft_output_kernel<QQ, true><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
+	} else {
+		NBL_SOFT_Q(g.q, soft_output_kernel<QQ><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
+	}
 	return hipGetLastError();
 }

@@ -121,6 +121,26 @@ int nblh_demod_general(int N, int p, int M, int L, const double *cons, const int
 	return 0;
 }
 
+// The prior-aware overload of CComm::DemodulateGeneral on B frames: prior [B][N p] (NULL: the function above).
+int nblh_demod_general_prior(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, const double *prior, double sigma,
+                             int metric, int B, double *out)
+{
+	if (!prior) return nblh_demod_general(N, p, M, L, cons, src, rx, sigma, metric, B, out);
+	if (N <= 0 || p < 1 || p > 8 || M < 2 || M > 256 || (M & (M - 1)) || L <= 0 || (metric != 0 && metric != 1)) return -1;
+	int m = 0;
+	while ((1 << m) < M) m++;
+	std::vector<char> seen((size_t)L * m, 0);
+	for (int i = 0; i < N * p; i++) {
+		if (src[i] < 0) continue;
+		if (src[i] >= L * m || seen[src[i]]) return -2;
+		seen[src[i]] = 1;
+	}
+	for (int b = 0; b < B; b++)
+		CComm::DemodulateGeneral(N, p, M, L, cons, src, rx + (size_t)b * L * 2, sigma, metric, prior + (size_t)b * N * p,
+		                         out + (size_t)b * N * ((1 << p) - 1));
+	return 0;
+}
+
 // Full simulation of one profile on the GPU; per Eb/N0 point: EbN0, errFrame, errSym, errBit, U_errFrame, frames, BER, SER, FER.
 int nblh_simulate(const char *profile, int device, double *rows, int max_rows)
 {

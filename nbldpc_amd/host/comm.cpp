@@ -447,6 +447,68 @@ void CComm::DemodulateGeneral(int N, int p, int M, int L, const double *cons, co
 	}
 }
 
+// include/nbldpc.h, "prior-aware general demodulator", statement by statement: the function above with d' in place of d.
+// prior [N p] per code bit; NULL IS the function above.
+void CComm::DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric,
+                              const double *prior, double *out)
+{
+	if (!prior) { DemodulateGeneral(N, p, M, L, cons, src, rx, sigma, metric, out); return; }
+	const int q = 1 << p;
+	int m = 0;
+	while ((1 << m) < M) m++;
+	std::vector<int> claim((size_t)L * m, -1); // label bit t -> the code bit g with src[g] == t
+	for (int g = 0; g < N * p; g++)
+		if (src[g] >= 0) claim[src[g]] = g;
+	std::vector<double> d(M), D(q);
+	for (int n = 0; n < N; n++) {
+		double *Ln = out + (size_t)n * (q - 1);
+		for (int a = 1; a < q; a++) Ln[a - 1] = 0.0;
+		std::vector<int> pts;
+		for (int j = 0; j < p; j++) {
+			const int t = src[n * p + j];
+			if (t >= 0) pts.push_back(t / m);
+		}
+		std::sort(pts.begin(), pts.end());
+		pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+		for (int s : pts) {
+			int owner[8], nown = 0;
+			for (int i = 0; i < m; i++) owner[i] = -1;
+			for (int j = 0; j < p; j++) {
+				const int t = src[n * p + j];
+				if (t >= 0 && t / m == s) { owner[t % m] = j; nown++; }
+			}
+			const double re = rx[2 * s], im = rx[2 * s + 1];
+			for (int c = 0; c < M; c++) {
+				const double cr = cons[2 * c], ci = cons[2 * c + 1];
+				d[c] = (re - cr) * (re - cr) + (im - ci) * (im - ci);
+				double A = 0.0;
+				for (int i = 0; i < m; i++)
+					if (owner[i] < 0 && claim[(size_t)s * m + i] >= 0 && ((c >> (m - 1 - i)) & 1)) A = A + prior[claim[(size_t)s * m + i]];
+				d[c] = d[c] - (2 * sigma * sigma) * A;
+			}
+			for (int a = 0; a < q; a++) {
+				auto compatible = [&](int c) {
+					for (int i = 0; i < m; i++)
+						if (owner[i] >= 0 && ((c >> (m - 1 - i)) & 1) != ((a >> owner[i]) & 1)) return false;
+					return true;
+				};
+				bool first = true;
+				double dmin = 0.0;
+				for (int c = 0; c < M; c++)
+					if (compatible(c) && (first || d[c] < dmin)) { dmin = d[c]; first = false; }
+				if (metric == NBL_DEMOD_MAXLOG || nown == m) D[a] = dmin;
+				else {
+					double sum = 0.0;
+					for (int c = 0; c < M; c++)
+						if (compatible(c)) sum = sum + exp(-(d[c] - dmin) / (2 * sigma * sigma));
+					D[a] = dmin - (2 * sigma * sigma) * log(sum);
+				}
+			}
+			for (int a = 1; a < q; a++) Ln[a - 1] = Ln[a - 1] + (D[0] - D[a]) / (2 * sigma * sigma);
+		}
+	}
+}
+
 int CComm::TakeDecoded(const int *decoded, bool converged) // Comm.cpp:421-443
 {
 	DecodeCorrect = converged;

@@ -47,6 +47,9 @@ public:
 	// = 2^m points cons [M][2], src [N p], samples rx [L][2] -> out [N][2^p - 1].  src is taken as checked (each t once, below L m).
 	static void DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric,
 	                              double *out);
+	// the prior-aware form (include/nbldpc.h, nbl_decode_batch_samples_prior): prior [N p] per code bit; NULL IS the function above
+	static void DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric,
+	                              const double *prior, double *out);
 	int GenerateMessage();
 	int GenPN();
 	void CRCEncode(int *seqOut, const int *seqIn, int seqInLen, int crcLen, int crc24Type);

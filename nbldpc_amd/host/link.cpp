@@ -55,6 +55,11 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 		for (auto &x : extra)
 			if (x->SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data(), lanes[0]->demod_metric) != 0) { error = x->LastError(); return false; }
 	}
+	if (!device_demod && code.IddPasses() > 1) {
+		error = "NBL_IDD_PASSES=" + std::to_string(code.IddPasses()) + ": iterative demapping runs behind the device-side demodulator; NBL_DEVICE_DEMOD=0 switches that off";
+		std::cerr << error << std::endl;
+		return false;
+	}
 	if (device_tx) {
 		CComm &l0 = *lanes[0];
 		std::vector<uint16_t> gen;

@@ -45,6 +45,29 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 
 	if (device < 0) return true; // host-only use (link-chain front-end, encoder): no decoder handle is created
 
+	idd_passes = 1;
+	idd_soft = NBL_SOFT_MAXLOG;
+	if (const char *e = getenv("NBL_IDD_PASSES")) {
+		char *end = nullptr;
+		const long k = strtol(e, &end, 10);
+		if (end == e || *end || k < 1 || k > 1000) {
+			error = std::string("NBL_IDD_PASSES=") + e + ": the number of demapping passes must be an integer from 1 up";
+			std::cerr << error << std::endl;
+			return false;
+		}
+		idd_passes = (int)k;
+	}
+	if (const char *e = getenv("NBL_IDD_SOFT")) {
+		const std::string v(e);
+		if (v == "maxlog") idd_soft = NBL_SOFT_MAXLOG;
+		else if (v == "logsum") idd_soft = NBL_SOFT_LOGSUM;
+		else {
+			error = "NBL_IDD_SOFT=" + v + ": unknown metric (maxlog, logsum)";
+			std::cerr << error << std::endl;
+			return false;
+		}
+	}
+
 	// hand the graph and the parameters to the device library
 	std::vector<int32_t> vchk, vh, cvar, ch;
 	for (int n = 0; n < CodeLen; n++) for (int d = 0; d < VarDegree[n]; d++) { vchk.push_back(VarLink[n][d]); vh.push_back(VarLinkGFe[n][d]); }
@@ -231,6 +254,12 @@ int CNBLDPC::DecodingBatch(const double *L_ch, int B, int *out, uint8_t *converg
 int CNBLDPC::SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src, int metric)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }
+	if (idd_passes > 1 && (mod_order == 2 || mod_order == GFq)) {
+		error = "NBL_IDD_PASSES=" + std::to_string(idd_passes) + ": iterative demapping needs the general demodulator (a modulation order other than 2 and GFq); "
+		        "this one has no foreign bits and every pass would be the same decode";
+		std::cerr << error << std::endl;
+		return -1;
+	}
 	nbl_demod_desc dm = {mod_order, n_mod_sym, constellation, src};
 	nbl_demod_ext ext = {metric, 0}; // orders 2 and GFq: the two reference-pinned paths, the metric is not read
 	nbl_status st = nbl_set_demodulator_ex(dec, &dm, &ext);
@@ -241,7 +270,9 @@ int CNBLDPC::SetDemodulator(int mod_order, int n_mod_sym, const double *constell
 int CNBLDPC::DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }
-	nbl_status st = nbl_decode_batch_samples(dec, rx, sigma, B, out, converged, iters);
+	const nbl_idd_params idd = {idd_passes, idd_soft};
+	nbl_status st = idd_passes > 1 ? nbl_decode_batch_samples_idd(dec, rx, sigma, B, &idd, out, converged, iters, nullptr)
+	                               : nbl_decode_batch_samples(dec, rx, sigma, B, out, converged, iters);
 	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
 	return 0;
 }
@@ -281,7 +312,9 @@ int CNBLDPC::ChannelBatch(int slot, const unsigned char *tx_index, const unsigne
 int CNBLDPC::DecodingBatchResident(int slot, double sigma, int B, int *out, uint8_t *converged, int *iters)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }
-	nbl_status st = nbl_decode_batch_resident(dec, slot, sigma, B, out, converged, iters);
+	const nbl_idd_params idd = {idd_passes, idd_soft};
+	nbl_status st = idd_passes > 1 ? nbl_decode_batch_resident_idd(dec, slot, sigma, B, &idd, out, converged, iters, nullptr)
+	                               : nbl_decode_batch_resident(dec, slot, sigma, B, out, converged, iters);
 	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
 	return 0;
 }

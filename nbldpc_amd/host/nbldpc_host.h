@@ -60,6 +60,7 @@ public:
 	int CountErrors(int slot, int B, int *err_sym, int *err_bit, uint8_t *crc_ok);
 	const std::string &LastError() const { return error; }
 	nbl_decoder *Handle() const { return dec; }
+	int IddPasses() const { return idd_passes; } // NBL_IDD_PASSES as Initial read it
 
 private:
 	// encoder state (InitialEncode NBLDPC.cpp:477-560)
@@ -69,4 +70,7 @@ private:
 	bool LoadMatRepr(std::vector<uint8_t> &m);
 	nbl_decoder *dec = nullptr;
 	std::string error;
+	// NBL_IDD_PASSES=k (default 1), NBL_IDD_SOFT=maxlog|logsum: DecodingBatchSamples and DecodingBatchResident go through the
+	// iterative-demapping loop (nbl_decode_batch_samples_idd / nbl_decode_batch_resident_idd); above 1 needs a general demodulator
+	int idd_passes = 1, idd_soft = NBL_SOFT_MAXLOG;
 };

@@ -26,6 +26,7 @@ def load():
         L.nblh_frontend.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.nblh_channel.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.nblh_demod_general.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
+        L.nblh_demod_general_prior.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
         L.nblh_simulate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int]
         L.nblh_encode.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
         L.nblh_generator.argtypes = [C.c_char_p, C.c_void_p]
@@ -101,6 +102,25 @@ def demod_general(N, p, points, src, rx, sigma, metric):
     rc = load().nblh_demod_general(N, p, points.shape[0], L, points.ctypes.data, src.ctypes.data, rx.ctypes.data, float(sigma), int(metric), B, out.ctypes.data)
     if rc != 0:
         raise RuntimeError(f"nblh_demod_general rc={rc}")
+    return out
+
+
+def demod_general_prior(N, p, points, src, rx, sigma, metric, prior):
+    """The prior-aware overload of CComm::DemodulateGeneral (include/nbldpc.h, nbl_decode_batch_samples_prior): prior [B][N p] bit LLRs
+    ln P(1) / P(0) per code bit, or None (then it IS demod_general).  No GPU."""
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    src = np.ascontiguousarray(src, dtype=np.int32)
+    rx = np.ascontiguousarray(rx, dtype=np.float64)
+    B, L = rx.shape[0], rx.shape[1]
+    assert src.shape == (N * p,) and rx.shape == (B, L, 2) and points.shape[1] == 2
+    if prior is not None:
+        prior = np.ascontiguousarray(prior, dtype=np.float64)
+        assert prior.shape == (B, N * p), prior.shape
+    out = np.zeros((B, N, (1 << p) - 1))
+    rc = load().nblh_demod_general_prior(N, p, points.shape[0], L, points.ctypes.data, src.ctypes.data, rx.ctypes.data,
+                                         None if prior is None else prior.ctypes.data, float(sigma), int(metric), B, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"nblh_demod_general_prior rc={rc}")
     return out
 
 
