@@ -172,7 +172,8 @@ void nbl_destroy(nbl_decoder *dec);
  * extension parameters).  Refused at creation, before the device is touched, with a message: NBL_ERR_ARG for a layer index below 0,
  * an empty layer below the largest index used, two checks of one layer sharing a variable (the message names both checks and the
  * variable); NBL_ERR_UNSUPPORTED for any other method (methods 1, 4 and 7 damp their variable-to-check messages against the
- * previous iteration's; T-EMS has its layered schedule behind nbl_create_layered_ex below, methods 1 and 7 stay flooding-only); and
+ * previous iteration's; T-EMS has its layered schedule behind nbl_create_layered_ex below, log-QSPA behind nbl_create_layered_bp, method
+ * 7 stays flooding-only); and
  * everything nbl_create refuses, the same way.
  * Every decode call, the demodulator, channel, transmitter and error count work unchanged on such a decoder.  nbl_read_state returns
  * post (with nbl_set_record_state) and c2v as defined above; EMS never materialises v2c: a non-NULL v2c is NBL_ERR_UNSUPPORTED.
@@ -205,14 +206,46 @@ nbl_status nbl_get_layers(const nbl_decoder *dec, int32_t *layer_of, int32_t *n_
  *   fixed_iters, poll_every, the active list and the device-buffer entry points keep their meaning.
  * nbl_create_layered_ex: flags == 0 IS nbl_create_layered (the same refusals, the same texts).  NBL_LAYERED_DAMPED with NBL_METHOD_TEMS
  * runs the schedule above; with NBL_METHOD_EMS the flag is inert (EMS has no damping: the decoder is nbl_create_layered's); any other
- * method is NBL_ERR_UNSUPPORTED (log-QSPA agrees with the reference-pinned oracle to 1e-9 only and BS-TEMS has no single-check oracle
- * entry point, so neither schedule could be pinned bit for bit); an unknown flag bit is NBL_ERR_ARG.  Everything nbl_create refuses is
+ * method is NBL_ERR_UNSUPPORTED (log-QSPA has its own entry point, nbl_create_layered_bp below, with its own parity statement; BS-TEMS
+ * has no single-check oracle entry point, so its schedule could not be pinned); an unknown flag bit is NBL_ERR_ARG.  Everything nbl_create refuses is
  * refused the same way (T-EMS with log2(q) * maxdc > 32 included), and a shape whose check needs more than 160 KB of LDS is refused
  * here, not at the first decode; all of it before the device is touched.  On a damped T-EMS decoder nbl_read_state returns v2c as
  * defined above (variable-major edge order, like c2v) instead of refusing it; nbl_get_layers works. */
 #define NBL_LAYERED_DAMPED 1
 nbl_status nbl_create_layered_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                                  const nbl_params *params, const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
+/* ---- the layered schedule for log-QSPA, with its per-edge damping ---------------------------------------------------------------
+ * The reference's log-QSPA damps like its T-EMS, per edge against the SAME EDGE's vector of the previous iteration (NBLDPC.cpp:730-741),
+ * with the blend 0.5 old + 0.5 new where the hard decisions differ; so a check visited in its layer can do it itself here too.
+ * Defined operation by operation (tests/layered_bp_ref.py restates it in numpy on top of the oracle's log-QSPA check-node update;
+ * DESIGN.md section 5j):
+ *   Layer assignment: as above -- the same validity rules, the same refusal texts, the same nbl_layer_greedy for layer_of == NULL.
+ *   State: c2v[E], all zero before iteration 1; v2c[E], with v2c[(m,k)] = L_ch[n] for the edge's variable n before iteration 1
+ *   (:647-655).  Vectors have q slots; slot 0 is 0.  Iteration it = 1 .. max_iter:
+ *   1. Tentative decision and syndrome exactly as flooding (:676-709).  The first zero syndrome freezes out_sym, sets converged and
+ *      iters = it (and, with fixed_iters == 0, ends the frame: its c2v AND v2c stay as iteration it-1 left them).
+ *   2. For l = 0 .. n_layers-1, for every check m with layer_of[m] == l:
+ *        for every edge k of m, with variable n:
+ *          P = L_ch[n];  P += c2v[e] for each edge e of n, in n's edge order, reading the CURRENT values;  raw = P - c2v[(m,k)]
+ *          old = v2c[(m,k)]
+ *          in_k = raw, unless DecideLLRVector(raw) != DecideLLRVector(old): then in_k[a] = 0.5 * old[a] + 0.5 * raw[a], each product
+ *          rounded, then the sum rounded, no contraction (:739)
+ *          v2c[(m,k)] = in_k
+ *        c2v[(m, .)] = the log-QSPA check-node update of in_0 .. in_{dc-1} (:747-767), as every log-QSPA kernel of this library
+ *        evaluates it (FP64 log-sum-exp; the reference's is 80-bit and sequential).
+ *   Parity is the method's own, as for flooding log-QSPA: hard decisions, converged flags and iteration counts equal those of the
+ *   FP64 restatement, post / c2v / v2c agree with it within 1e-9 of the largest magnitude; not bit for bit.
+ *   fixed_iters, poll_every, the active list and the device-buffer entry points keep their meaning; so do bit-LLR input, soft output
+ *   (plain and extrinsic), the demodulators, channel, transmitter, error count and the iterative-demapping loop.
+ * nbl_create_layered_bp: nbl_create with this schedule.  NBL_METHOD_BP only (no OSD, no extension parameters); there are no flags.
+ * Refused at creation, before the device is touched, with a message: NBL_ERR_UNSUPPORTED for any method but 1 (the message names
+ * method 1 and points to nbl_create_layered and nbl_create_layered_ex); every assignment error of nbl_create_layered, with its status
+ * and text; everything nbl_create refuses, the same way.  No shape is refused for its LDS: a check takes (3 maxdc + 5) q 8 bytes,
+ * 59,392 B at q = 256 and degree 8.  nbl_read_state returns post (with nbl_set_record_state), c2v and v2c as defined above, both in
+ * variable-major edge order; nbl_get_layers works. */
+nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
+                                 const nbl_params *params, const int32_t *layer_of, int device, nbl_decoder **out);
 
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the

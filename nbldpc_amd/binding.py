@@ -19,7 +19,7 @@ SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
 SOFT_EXTRINSIC = 1
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_create_layered_bp", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
@@ -92,6 +92,8 @@ def load_library():
         L.nbl_create_layered.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_create_layered_ex.restype = C.c_int
         L.nbl_create_layered_ex.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_create_layered_bp.restype = C.c_int
+        L.nbl_create_layered_bp.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_get_layers.restype = C.c_int
         L.nbl_get_layers.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.nbl_destroy.argtypes = [C.c_void_p]
@@ -195,12 +197,13 @@ class Decoder:
     (datafiles.gf_matrices(q, as_loaded=True)).  layers: None = the flooding schedule; "greedy" or an int array [M] (a layer per
     check) = the layered schedule through nbl_create_layered (EMS only; no bs_* / osd_* parameters go with it).  damped (with layers
     only): None = nbl_create_layered as before; anything else goes through nbl_create_layered_ex with flags = int(damped), so True =
-    NBL_LAYERED_DAMPED: T-EMS under the layered schedule with its per-edge damping (inert for EMS), False = flags 0."""
+    NBL_LAYERED_DAMPED: T-EMS under the layered schedule with its per-edge damping (inert for EMS), False = flags 0.  bp=True (with
+    layers, without damped): nbl_create_layered_bp, log-QSPA under the layered schedule with its 0.5 / 0.5 per-edge damping."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None, layers=None, damped=None):
+                 gf_mat=None, layers=None, damped=None, bp=False):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -212,6 +215,10 @@ class Decoder:
         h = C.c_void_p()
         if damped is not None and layers is None:
             raise ValueError("damped: the flag belongs to the layered schedule (give layers='greedy' or an assignment)")
+        if bp and layers is None:
+            raise ValueError("bp: nbl_create_layered_bp is a layered schedule (give layers='greedy' or an assignment)")
+        if bp and damped is not None:
+            raise ValueError("bp: nbl_create_layered_bp takes no flags (its damping is part of the schedule): leave damped out")
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
                 raise ValueError("layers: nbl_create_layered takes neither OSD nor extension parameters")
@@ -219,7 +226,9 @@ class Decoder:
             if self._layer_of is not None and self._layer_of.shape != (code.M,):
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
             lay = None if self._layer_of is None else self._layer_of.ctypes.data
-            if damped is None:
+            if bp:
+                rc = self.lib.nbl_create_layered_bp(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
+            elif damped is None:
                 rc = self.lib.nbl_create_layered(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
             else:
                 rc = self.lib.nbl_create_layered_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,

@@ -44,8 +44,9 @@ struct nbl_decoder {
 	                            // have to be cleared on every call)
 	const double *last_c2v = nullptr;
 	bool last_fused = false;    // the last decode ran fused iterations (nbl_read_state picks the c2v buffer per codeword)
-	// layered (check-serial) schedule (nbl_create_layered / nbl_create_layered_ex): one c2v buffer updated in place; EMS keeps no v2c,
-	// T-EMS (NBL_LAYERED_DAMPED) keeps the per-edge v2c its damping reads, updated in place by the edge's check
+	// layered (check-serial) schedule (nbl_create_layered / nbl_create_layered_ex / nbl_create_layered_bp): one c2v buffer updated in
+	// place; EMS keeps no v2c, T-EMS (NBL_LAYERED_DAMPED) and log-QSPA keep the per-edge v2c their damping reads, updated in place by the
+	// edge's check
 	bool layered = false;
 	int n_layers = 0;
 	std::vector<int> h_layer_of; // [M] the assignment in use
@@ -480,8 +481,9 @@ extern "C" int32_t nbl_layer_greedy(const nbl_code_desc *code, int32_t *layer_of
 	return layer_greedy(N, M, coff, code->chk_var, layer_of);
 }
 
-// nbl_create_layered's / nbl_create_layered_ex's request: layer_of == NULL asks for the greedy assignment; flags: NBL_LAYERED_*
-struct LayerReq { const int32_t *layer_of; uint32_t flags; };
+// nbl_create_layered's / nbl_create_layered_ex's / nbl_create_layered_bp's request: layer_of == NULL asks for the greedy assignment;
+// flags: NBL_LAYERED_*; bp: the log-QSPA entry point (method 1 alone, its own damping: no flag)
+struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out);
@@ -495,14 +497,21 @@ extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *
 extern "C" nbl_status nbl_create_layered(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                          const int32_t *layer_of, int device, nbl_decoder **out)
 {
-	const LayerReq lay = {layer_of, 0};
+	const LayerReq lay = {layer_of, 0, false};
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
 }
 
 extern "C" nbl_status nbl_create_layered_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                             const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
-	const LayerReq lay = {layer_of, flags};
+	const LayerReq lay = {layer_of, flags, false};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
+}
+
+extern "C" nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                            const int32_t *layer_of, int device, nbl_decoder **out)
+{
+	const LayerReq lay = {layer_of, 0, true};
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
 }
 
@@ -529,10 +538,13 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	std::string field_err;
 	const int poly = validate_field(q, gf_mul, gf_inv, field_err);
 	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
-	if (lay && (lay->flags & NBL_LAYERED_DAMPED) && params->method != NBL_METHOD_EMS && params->method != NBL_METHOD_TEMS)
+	if (lay && lay->bp && params->method != NBL_METHOD_BP)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_layered_bp runs log-QSPA (method 1) only: the layered schedule of EMS (method 2) is behind "
+		                                                 "nbl_create_layered, that of T-EMS (method 4) behind nbl_create_layered_ex with NBL_LAYERED_DAMPED");
+	if (lay && !lay->bp && (lay->flags & NBL_LAYERED_DAMPED) && params->method != NBL_METHOD_EMS && params->method != NBL_METHOD_TEMS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the damped layered schedule (NBL_LAYERED_DAMPED) is defined for T-EMS (method 4), and for EMS (method 2), which "
 		                                                 "has no damping, as the plain layered schedule: log-QSPA (method 1) and BS-TEMS (method 7) stay flooding-only");
-	if (lay && params->method != NBL_METHOD_EMS && !((lay->flags & NBL_LAYERED_DAMPED) && params->method == NBL_METHOD_TEMS))
+	if (lay && !lay->bp && params->method != NBL_METHOD_EMS && !((lay->flags & NBL_LAYERED_DAMPED) && params->method == NBL_METHOD_TEMS))
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the layered schedule is defined for EMS (method 2) only: the other methods damp against the previous iteration's "
 		                                                 "decision in their variable-node pass and stay flooding-only");
 	switch (params->method) {
@@ -649,10 +661,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	int n_layers = 0;
 	if (lay) {
 		// (the layered kernel is the general one: no specialised shape stands in for it, so the LDS bound holds for every shape)
+		// (log-QSPA: (3 maxdc + 5) q 8 bytes, at most 59,392 B at q = 256 and degree 8 -- nothing to refuse)
 		if (params->method == NBL_METHOD_TEMS) {
 			if (nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");
-		} else if (nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
+		} else if (params->method == NBL_METHOD_EMS && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
 			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
 		}
 		layer_of.assign(M, 0);
@@ -940,10 +953,16 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			HIP_TRY(d, mark(c, 0, st));
 			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
 			HIP_TRY(d, mark(c, 1, st));
-			// (T-EMS: each check also damps its inputs against the v2c buffer and updates it in place; init_kernel has set v2c = L_ch)
+			// (T-EMS, log-QSPA: each check also damps its inputs against the v2c buffer and updates it in place; init_kernel has set
+			// v2c = L_ch)
 			for (int l = 0; l < d->n_layers; l++) {
-				if (c.plan.cn == NBL_CN_TEMS_LAYERED) HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
-				else HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l], st));
+				const int off = d->h_lay_off[l], cnt = d->h_lay_off[l + 1] - off;
+				switch (c.plan.cn) {
+				case NBL_CN_EMS_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				case NBL_CN_TEMS_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				case NBL_CN_BP_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				default: d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED;
+				}
 			}
 			HIP_TRY(d, mark(c, 2, st));
 			if (count) { d->launches[0]++; d->launches[1]++; d->launches[2] += d->n_layers; }
@@ -1898,7 +1917,7 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 		else rc = grab(d->w.post + (size_t)b * N * q, nullptr, N, post);
 	}
 	if (!rc && v2c) {
-		if (d->layered && d->prm.method != NBL_METHOD_TEMS) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
+		if (d->layered && d->prm.method == NBL_METHOD_EMS) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
 		else if (!d->w.v2c) { d->err = "v2c is not kept in HBM on the fused path unless state recording is on (nbl_set_record_state)"; rc = NBL_ERR_ARG; }
 		else rc = grab(d->w.v2c + (size_t)b * E * q, nullptr, E, v2c);
 	}

@@ -31,6 +31,10 @@ hipError_t nbl_launch_cn_ems_layered(const NblGraphDev &g, const NblWork &w, con
 size_t nbl_tems_layered_lds_bytes(int q, int maxdc, int nc);
 hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// damped layered schedule for log-QSPA (nbl_cn_bp_layered.hip): the checks of one layer; inputs formed and damped as for T-EMS (0.5 / 0.5),
+// then the programme of nbl_cn_bp_core.h.  LDS: (3 maxdc + 5) q 8 bytes, at most 59,392 B for the shapes the ABI accepts
+hipError_t nbl_launch_cn_bp_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 size_t nbl_ems256_lds_bytes(int nm);
 hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);

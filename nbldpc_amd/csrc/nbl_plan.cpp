@@ -32,7 +32,7 @@ NblShape nbl_shape(const nbl_code_desc *code)
 
 static const char *const cn_names[NBL_CN_COUNT] = {
 	"ems256", "ems_small", "ems64", "ems", "tems64", "tems256", "tems_small", "tems", "bp256", "bp64", "bp_small", "bp",
-	"bstems", "ems_layered", "tems_layered", "none"};
+	"bstems", "ems_layered", "tems_layered", "none", "bp_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 
@@ -40,9 +40,9 @@ NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext 
                  bool small_on)
 {
 	NblPlan pl{NBL_CN_NONE, false, false, true};
-	if (layered) { // one c2v buffer updated in place: never fused; T-EMS keeps the v2c its damping reads
-		pl.cn = prm.method == NBL_METHOD_TEMS ? NBL_CN_TEMS_LAYERED : NBL_CN_EMS_LAYERED;
-		pl.want_v2c = prm.method == NBL_METHOD_TEMS;
+	if (layered) { // one c2v buffer updated in place: never fused; T-EMS and log-QSPA keep the v2c their damping reads
+		pl.cn = prm.method == NBL_METHOD_TEMS ? NBL_CN_TEMS_LAYERED : prm.method == NBL_METHOD_BP ? NBL_CN_BP_LAYERED : NBL_CN_EMS_LAYERED;
+		pl.want_v2c = prm.method == NBL_METHOD_TEMS || prm.method == NBL_METHOD_BP;
 		return pl;
 	}
 	NblCn general = NBL_CN_NONE, special = NBL_CN_NONE;

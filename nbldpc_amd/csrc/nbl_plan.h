@@ -9,6 +9,7 @@ enum NblCn {
 	NBL_CN_BP256, NBL_CN_BP64, NBL_CN_BP_SMALL, NBL_CN_BP,
 	NBL_CN_BSTEMS, NBL_CN_EMS_LAYERED, NBL_CN_TEMS_LAYERED,
 	NBL_CN_NONE, // method 6: no iteration
+	NBL_CN_BP_LAYERED,
 	NBL_CN_COUNT
 };
 

@@ -97,22 +97,26 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	nbl_osd_params op = {sim.OSD_order, sim.OSD_flag, sim.OSD_factor, sim.crcLen, sim.crc_correctLen, gf_mat.data()};
 	// NBL_SCHEDULE=layered: the layered (check-serial) schedule with the library's greedy layers in place of flooding (off by default;
 	// EMS without OSD only -- nbl_create_layered says why).  NBL_SCHEDULE=layered-damped: the same through nbl_create_layered_ex with
-	// NBL_LAYERED_DAMPED, which also serves T-EMS (its per-edge damping done by the check) and leaves EMS as it is; no OSD either
+	// NBL_LAYERED_DAMPED, which also serves T-EMS (its per-edge damping done by the check) and leaves EMS as it is; no OSD either.
+	// NBL_SCHEDULE=layered-bp: log-QSPA (method 1) without OSD through nbl_create_layered_bp
 	const char *sched = getenv("NBL_SCHEDULE");
 	const bool damped = sched && std::string(sched) == "layered-damped";
-	const bool layered = damped || (sched && std::string(sched) == "layered");
+	const bool lay_bp = sched && std::string(sched) == "layered-bp";
+	const bool layered = damped || lay_bp || (sched && std::string(sched) == "layered");
 	if (sched && !layered && std::string(sched) != "flooding") {
-		error = std::string("NBL_SCHEDULE=") + sched + ": unknown schedule (flooding, layered, layered-damped)";
+		error = std::string("NBL_SCHEDULE=") + sched + ": unknown schedule (flooding, layered, layered-damped, layered-bp)";
 		std::cerr << error << std::endl;
 		return false;
 	}
 	if (layered && osd) {
-		error = damped ? "NBL_SCHEDULE=layered-damped: the damped layered schedule is defined for T-EMS (method 4) and EMS (method 2) without OSD only"
-		               : "NBL_SCHEDULE=layered: the layered schedule is defined for EMS (method 2) without OSD only";
+		error = lay_bp   ? "NBL_SCHEDULE=layered-bp: the layered log-QSPA schedule is defined for log-QSPA (method 1) without OSD only"
+		        : damped ? "NBL_SCHEDULE=layered-damped: the damped layered schedule is defined for T-EMS (method 4) and EMS (method 2) without OSD only"
+		                 : "NBL_SCHEDULE=layered: the layered schedule is defined for EMS (method 2) without OSD only";
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = damped    ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
+	nbl_status st = lay_bp    ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
+	                : damped  ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
 	                : layered ? nbl_create_layered(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
 	                          : nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
 	                                           osd ? &op : nullptr, device, &dec);
