@@ -495,6 +495,71 @@ nbl_status nbl_decode_batch_samples_idd(nbl_decoder *dec, const double *rx, doub
 nbl_status nbl_decode_batch_resident_idd(nbl_decoder *dec, int32_t slot, double sigma, int32_t B, const nbl_idd_params *idd,
                                          int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used /* [B] or NULL */);
 
+/* ---- flat fading: per-sample channel gains in the demodulators, Rayleigh block fading on the device ---------------------------------
+ * Coherent reception of y = h x + n with a known complex gain h per received sample.  Nothing in the reference computes any of this;
+ * the operations are defined here, operation by operation, so that independent implementations agree (tests/fading_ref.py restates
+ * them in numpy, with a probability-domain brute force beside the general demodulator).  All arithmetic is IEEE
+ * double; each product and each sum is rounded on its own, no contraction.
+ *
+ * Gains.  gain is [B][L][2] doubles (Real, Image), laid out like rx: one gain per received sample.
+ * Faded point.  For sample s with gain (hr, hi) and table point c = (cr, ci):
+ *     pr = hr * cr - hi * ci
+ *     pi = hr * ci + hi * cr
+ * Demodulators with gains.
+ *   General path:  d_s(c) = (re - pr) * (re - pr) + (im - pi) * (im - pi).  Everything else of the general demodulator's definition
+ *     holds word for word: own and foreign positions, C_s(a), max-log and log-sum, the prior term d' = d - (2 sigma sigma) * A, the
+ *     ascending orders.
+ *   One point per symbol (mod_order == q, not forced general): the existing expression with the faded points of sample s = src[n]
+ *     (p0 of table point 0, pa of table point a) in place of the table's:
+ *       num = (2 * re - p0r - par) * (par - p0r) + (2 * im - p0i - pai) * (pai - p0i);   L = num / (2 * sigma * sigma)
+ *   BPSK path:  z = hr * re + hi * im, and the bit LLR is -2 * z / (sigma * sigma): the existing expression with z in place of re.
+ *     Punctured bits stay 0.0.
+ *   Consequences:
+ *     - A gain of (1, 0) everywhere gives LLRs equal as numbers to the gain-less call's; only the sign of a zero may differ.
+ *     - On the general and q-ary paths a gain that is constant over a frame gives LLRs bit-identical to the gain-less demodulator set
+ *       up with the pre-faded table (pr, pi).
+ *     - On the BPSK path a real positive gain g gives the gain-less demodulator's LLRs for samples g * re.
+ *   nbl_decode_batch_samples_csi: nbl_decode_batch_samples_prior with that demodulator.  gain == NULL IS nbl_decode_batch_samples_prior
+ *   and launches the kernel that call launches.  nbl_decode_batch_samples_idd_csi: the loop of nbl_decode_batch_samples_idd with the
+ *   gain-aware demodulator in every pass; when passes 2 and later gather the unconverged codewords into dense buffers, their gains are
+ *   gathered with them.  gain == NULL IS nbl_decode_batch_samples_idd.  Both refuse what the calls they extend refuse.
+ *
+ * Rayleigh block fading on the device.  nbl_set_fading(dec, f): model NBL_FADING_NONE or NBL_FADING_RAYLEIGH; coherence >= 1 = the
+ *   number of consecutive samples that share one gain.  f == NULL or NONE gives AWGN again, exactly as before the call.  An unknown
+ *   model or coherence < 1 is NBL_ERR_ARG with a message; a refused call leaves the previous setting in force.  Legal any time after
+ *   creation; it survives nbl_set_demodulator*, the block count follows the current L.
+ *   With Rayleigh set, a frame of a lane is formed in this order:
+ *     1. nblk = ceil(L / coherence)
+ *     2. for block k = 0 .. nblk-1, in order, with S = sqrt(0.5) as a double:  hr_k = Rand_Norm(0, S);  hi_k = Rand_Norm(0, S)
+ *        (four uniform draws per block, Rand.cpp:31-37's expression order)
+ *     3. the noise exactly as Channel_AWGN draws it (Comm.cpp:328-337): nr, ni per sample, 4 L uniform draws
+ *     4. for sample s, k = s / coherence, transmitted point (cr, ci):
+ *          RX.Real  = (hr_k * cr - hi_k * ci) + nr
+ *          RX.Image = (hr_k * ci + hi_k * cr) + ni
+ *   A frame therefore moves a lane's generator 4 nblk + 4 L draws: nbl_channel_draws(dec) returns that number, 4 L without fading
+ *   (0 before a demodulator is set).  E|h|^2 = 1, so the Eb/N0 -> sigma relation stays as it is.
+ *   With Rayleigh set nbl_decode_batch_noise, nbl_channel_batch and nbl_transmit_batch form faded samples and keep the per-sample
+ *   gains beside the samples -- in a slot they stay resident, one buffer per slot, grown on demand and counted in
+ *   nbl_workspace_bytes -- and nbl_decode_batch_noise, nbl_decode_batch_resident and nbl_decode_batch_resident_idd demodulate with
+ *   those gains.  A slot remembers whether it holds gains: a slot filled before nbl_set_fading decodes as AWGN.
+ *   nbl_read_gains: the gains [n][L][2] a slot holds for lanes b0 .. b0 + n - 1, for parity tests; NBL_ERR_ARG on a slot without gains.
+ * Out of scope: a per-sample noise variance, non-coherent reception, channel estimation, frequency-selective channels. */
+#define NBL_FADING_NONE 0
+#define NBL_FADING_RAYLEIGH 1
+typedef struct nbl_fading_desc {
+	int32_t model;               /* NBL_FADING_* */
+	int32_t coherence;           /* >= 1: consecutive samples that share one gain */
+} nbl_fading_desc;
+nbl_status nbl_decode_batch_samples_csi(nbl_decoder *dec, const double *rx, const double *gain /* HOST [B][L][2] or NULL */,
+                                        const double *prior /* HOST [B][N p] or NULL */, double sigma, int32_t B, int32_t *out_sym,
+                                        uint8_t *converged, int32_t *iters);
+nbl_status nbl_decode_batch_samples_idd_csi(nbl_decoder *dec, const double *rx, const double *gain /* HOST [B][L][2] or NULL */, double sigma,
+                                            int32_t B, const nbl_idd_params *idd, int32_t *out_sym, uint8_t *converged, int32_t *iters,
+                                            int32_t *passes_used /* [B] or NULL */);
+nbl_status nbl_set_fading(nbl_decoder *dec, const nbl_fading_desc *f /* NULL: AWGN */);
+uint64_t nbl_channel_draws(const nbl_decoder *dec);
+nbl_status nbl_read_gains(nbl_decoder *dec, int32_t slot, int32_t b0, int32_t n, double *gain /* HOST [n][L][2] */);
+
 /* Message state of codeword b after the last decode call (host buffers, any may be NULL):
  * post [N][q-1], v2c [E][q-1], c2v [E][q-1], edges in variable-major order.  For parity tests.
  * post and c2v are the reference's members at return.  v2c differs for a codeword that CONVERGED at iteration k >= 2: the

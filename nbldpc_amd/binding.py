@@ -17,6 +17,7 @@ METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
 DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
 SOFT_EXTRINSIC = 1
+FADING_NONE, FADING_RAYLEIGH = 0, 1
 
 # every symbol include/nbldpc.h declares
 EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_create_layered_bp", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
@@ -24,7 +25,8 @@ EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
            "nbl_workspace_bytes", "nbl_decode_batch_bits", "nbl_decode_batch_bits_device", "nbl_soft_output", "nbl_soft_output_device",
-           "nbl_decode_batch_samples_prior", "nbl_soft_output_ex", "nbl_soft_output_device_ex", "nbl_decode_batch_samples_idd", "nbl_decode_batch_resident_idd")
+           "nbl_decode_batch_samples_prior", "nbl_soft_output_ex", "nbl_soft_output_device_ex", "nbl_decode_batch_samples_idd", "nbl_decode_batch_resident_idd",
+           "nbl_decode_batch_samples_csi", "nbl_decode_batch_samples_idd_csi", "nbl_set_fading", "nbl_channel_draws", "nbl_read_gains")
 
 
 class NblError(RuntimeError):
@@ -52,6 +54,10 @@ class ParamsExt(C.Structure):
 
 class IddParams(C.Structure):
     _fields_ = [("passes", C.c_int32), ("soft_metric", C.c_int32)]
+
+
+class FadingDesc(C.Structure):
+    _fields_ = [("model", C.c_int32), ("coherence", C.c_int32)]
 
 
 class OsdParams(C.Structure):
@@ -120,6 +126,17 @@ def load_library():
         L.nbl_decode_batch_samples_idd.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.POINTER(IddParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_decode_batch_resident_idd.restype = C.c_int
         L.nbl_decode_batch_resident_idd.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(IddParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_samples_csi.restype = C.c_int
+        L.nbl_decode_batch_samples_csi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nbl_decode_batch_samples_idd_csi.restype = C.c_int
+        L.nbl_decode_batch_samples_idd_csi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.POINTER(IddParams), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
+        L.nbl_set_fading.restype = C.c_int
+        L.nbl_set_fading.argtypes = [C.c_void_p, C.POINTER(FadingDesc)]
+        L.nbl_channel_draws.restype = C.c_uint64
+        L.nbl_channel_draws.argtypes = [C.c_void_p]
+        L.nbl_read_gains.restype = C.c_int
+        L.nbl_read_gains.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.nbl_read_state.restype = C.c_int
         L.nbl_read_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nbl_set_record_state.argtypes = [C.c_void_p, C.c_int32]
@@ -352,15 +369,26 @@ class Decoder:
             self.lib.nbl_set_demodulator_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
             self._chk(self.lib.nbl_set_demodulator_ex(self.h, C.byref(d), C.byref(ext)))
         self._dm_src, self._dm_cons = dm_src, dm_cons
+        self._tx_L = n_mod_sym
 
-    def decode_samples(self, rx, sigma, prior=None):
+    def decode_samples(self, rx, sigma, prior=None, gain=None):
         """rx: [B][L][2] received samples -> (out, converged, iters); L_ch is built on the device.  prior: None, or [B][N p] bit LLRs
-        ln P(1) / P(0) per code bit for the general demodulator (nbl_decode_batch_samples_prior)."""
+        ln P(1) / P(0) per code bit for the general demodulator (nbl_decode_batch_samples_prior).  gain: None, or [B][L][2] complex
+        channel gains, one per sample (nbl_decode_batch_samples_csi)."""
         rx = np.ascontiguousarray(rx, dtype=np.float64)
         B = rx.shape[0]
         out = np.zeros((B, self.code.N), dtype=np.int32)
         conv = np.zeros(B, dtype=np.uint8)
         iters = np.zeros(B, dtype=np.int32)
+        if gain is not None:
+            gain = np.ascontiguousarray(gain, dtype=np.float64)
+            assert gain.shape == rx.shape and rx.ndim == 3 and rx.shape[2] == 2, (gain.shape, rx.shape)
+            if prior is not None:
+                prior = np.ascontiguousarray(prior, dtype=np.float64)
+                assert prior.shape == (B, self.code.N * (self.code.q.bit_length() - 1)), prior.shape
+            self._chk(self.lib.nbl_decode_batch_samples_csi(self.h, rx.ctypes.data, gain.ctypes.data, None if prior is None else prior.ctypes.data, sigma, B,
+                                                            out.ctypes.data, conv.ctypes.data, iters.ctypes.data))
+            return out, conv, iters
         if prior is not None:
             prior = np.ascontiguousarray(prior, dtype=np.float64)
             assert prior.shape == (B, self.code.N * (self.code.q.bit_length() - 1)), prior.shape
@@ -371,9 +399,10 @@ class Decoder:
         self._chk(self.lib.nbl_decode_batch_samples(self.h, rx.ctypes.data, sigma, B, out.ctypes.data, conv.ctypes.data, iters.ctypes.data))
         return out, conv, iters
 
-    def decode_samples_idd(self, rx, sigma, passes, soft="maxlog"):
+    def decode_samples_idd(self, rx, sigma, passes, soft="maxlog", gain=None):
         """Iterative demapping (nbl_decode_batch_samples_idd): up to `passes` rounds of prior-aware demodulator + decode per codeword,
-        the prior of a round being the extrinsic bit LLRs (metric `soft`) of the round before -> (out, converged, iters, passes_used)"""
+        the prior of a round being the extrinsic bit LLRs (metric `soft`) of the round before -> (out, converged, iters, passes_used).
+        gain: None, or [B][L][2] channel gains for the demodulator of every pass (nbl_decode_batch_samples_idd_csi)."""
         rx = np.ascontiguousarray(rx, dtype=np.float64)
         B = rx.shape[0]
         out = np.zeros((B, self.code.N), dtype=np.int32)
@@ -381,9 +410,42 @@ class Decoder:
         iters = np.zeros(B, dtype=np.int32)
         used = np.zeros(B, dtype=np.int32)
         idd = IddParams(int(passes), int({"maxlog": SOFT_MAXLOG, "logsum": SOFT_LOGSUM}.get(soft, soft)))
+        if gain is not None:
+            gain = np.ascontiguousarray(gain, dtype=np.float64)
+            assert gain.shape == rx.shape and rx.ndim == 3 and rx.shape[2] == 2, (gain.shape, rx.shape)
+            self._chk(self.lib.nbl_decode_batch_samples_idd_csi(self.h, rx.ctypes.data, gain.ctypes.data, sigma, B, C.byref(idd), out.ctypes.data,
+                                                                conv.ctypes.data, iters.ctypes.data, used.ctypes.data))
+            return out, conv, iters, used
         self._chk(self.lib.nbl_decode_batch_samples_idd(self.h, rx.ctypes.data, sigma, B, C.byref(idd), out.ctypes.data, conv.ctypes.data,
                                                         iters.ctypes.data, used.ctypes.data))
         return out, conv, iters, used
+
+    def set_fading(self, model=None, coherence=1):
+        """The device-side channel's fading (nbl_set_fading): model None / "awgn" / FADING_NONE = AWGN, "rayleigh" / FADING_RAYLEIGH =
+        Rayleigh block fading with `coherence` consecutive samples per gain"""
+        m = {None: FADING_NONE, "awgn": FADING_NONE, "none": FADING_NONE, "rayleigh": FADING_RAYLEIGH}.get(model, model)
+        if m == FADING_NONE:
+            self._chk(self.lib.nbl_set_fading(self.h, None))
+        else:
+            f = FadingDesc(int(m), int(coherence))
+            self._chk(self.lib.nbl_set_fading(self.h, C.byref(f)))
+
+    def channel_draws(self):
+        """uniform draws one frame of the device-side channel moves a lane's generator (nbl_channel_draws)"""
+        return int(self.lib.nbl_channel_draws(self.h))
+
+    def read_gains(self, slot, b0, n):
+        """the channel gains [n][L][2] a slot holds beside its samples (nbl_read_gains); refused on a slot without gains"""
+        gain = np.zeros((n, self._tx_L, 2))
+        self._chk(self.lib.nbl_read_gains(self.h, slot, b0, n, gain.ctypes.data))
+        return gain
+
+    def time_demod(self, slot, sigma, B, with_prior=False, with_gain=False):
+        """diagnostic: device milliseconds of one demodulator launch on the samples a slot holds (nbl_debug_time_demod_csi)"""
+        ms = C.c_double(0)
+        self.lib.nbl_debug_time_demod_csi.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+        self._chk(self.lib.nbl_debug_time_demod_csi(self.h, slot, sigma, B, int(with_prior), int(with_gain), C.byref(ms)))
+        return ms.value
 
     def decode_noise(self, tx_index, lane_state, sigma):
         """tx_index [B][L] uint8, lane_state [B][3] uint32 (CRand state before the frame): channel + demodulator + decode on the device"""

@@ -67,12 +67,24 @@ struct nbl_decoder {
 	size_t d_prior_cap = 0;
 	struct Idd {                       // buffers of the loop, grown on demand, counted in soft_bytes
 		double *rx[2] = {nullptr, nullptr};  // samples of the survivors, ping-pong (pass k reads one, the gather fills the other)
+		double *gain[2] = {nullptr, nullptr}; // their channel gains, when the call has gains
+		size_t gain_cap[2] = {0, 0};
 		int *idx[2] = {nullptr, nullptr};    // their batch positions
 		double *ext = nullptr, *prior = nullptr; // extrinsic bit LLRs of a pass [n][N p]; the survivors' rows of it = the next prior
 		int *res_out = nullptr, *res_iters = nullptr, *res_pass = nullptr; // [B][N], [B], [B]: results at batch positions
 		uint8_t *res_done = nullptr;
 		size_t rx_cap[2] = {0, 0}, idx_cap[2] = {0, 0}, ext_cap = 0, prior_cap = 0, out_cap = 0, iters_cap = 0, pass_cap = 0, done_cap = 0;
 	} idd;
+	// flat fading (nbl_set_fading, nbl_decode_batch_samples_csi)
+	int fade_model = NBL_FADING_NONE, fade_coh = 1;
+	uint32_t *d_jump_f = nullptr;      // [3][nblk + L] A^(4 k) mod m: the fading frame's positions (gains, then noise)
+	int jump_f_pos = 0;                // the position count d_jump_f was made for
+	double *d_gain = nullptr;          // [B][L][2] gains beside d_rx: staging of a host array, or what the channel of nbl_decode_batch_noise formed
+	size_t d_gain_cap = 0;
+	bool rx_gain = false;              // d_gain holds the gains of the samples in d_rx
+	double *d_gains[2] = {nullptr, nullptr}; // resident gains beside d_rxs, one per slot (filled on the channel thread)
+	size_t d_gains_cap[2] = {0, 0};
+	bool slot_gain[2] = {false, false};      // the slot's samples were formed under fading: its gains are valid
 	bool idd_sub = false;              // the last decode call was a loop with passes > 1: the workspace holds its last sub-batch
 	// bit-LLR input and soft output (nbl_decode_batch_bits, nbl_soft_output): staging of the host forms, grown on demand
 	double *d_lam = nullptr, *d_soft_sym = nullptr, *d_soft_bit = nullptr;
@@ -89,7 +101,7 @@ struct nbl_decoder {
 	unsigned *d_fcount = nullptr;
 	uint32_t *h_fidx = nullptr;  // pinned host mirrors
 	double *h_farg = nullptr, *h_fval = nullptr;
-	size_t noise_cap = 0, flag_cap = 0;
+	size_t noise_cap = 0, noise_pos = 0, flag_cap = 0;
 	double last_flag_frac = 0.0;
 	hipStream_t stream2 = nullptr; // the channel of batch k+1 runs here while batch k is decoded on `stream`
 	double *d_rxs[2] = {nullptr, nullptr}; // resident received samples of nbl_channel_batch, one per slot
@@ -257,7 +269,10 @@ extern "C" const char *nbl_last_error(const nbl_decoder *dec)
 	return both.c_str();
 }
 
-extern "C" size_t nbl_workspace_bytes(const nbl_decoder *dec) { return dec ? dec->ws_bytes + dec->soft_bytes : 0; }
+extern "C" size_t nbl_workspace_bytes(const nbl_decoder *dec)
+{
+	return dec ? dec->ws_bytes + dec->soft_bytes + dec->d_gain_cap + dec->d_gains_cap[0] + dec->d_gains_cap[1] : 0;
+}
 
 static nbl_status fail_create(nbl_decoder *d, nbl_status st, const std::string &msg)
 {
@@ -797,7 +812,8 @@ extern "C" void nbl_destroy(nbl_decoder *d)
 	if (d->d_dmdesc) (void)hipFree(d->d_dmdesc);
 	if (d->d_rx) (void)hipFree(d->d_rx);
 	for (void *p : {(void *)d->d_tinv, (void *)d->d_prior, (void *)d->idd.rx[0], (void *)d->idd.rx[1], (void *)d->idd.idx[0], (void *)d->idd.idx[1],
-	                (void *)d->idd.ext, (void *)d->idd.prior, (void *)d->idd.res_out, (void *)d->idd.res_iters, (void *)d->idd.res_pass, (void *)d->idd.res_done})
+	                (void *)d->idd.ext, (void *)d->idd.prior, (void *)d->idd.gain[0], (void *)d->idd.gain[1], (void *)d->d_gain, (void *)d->d_gains[0],
+	                (void *)d->d_gains[1], (void *)d->d_jump_f, (void *)d->idd.res_out, (void *)d->idd.res_iters, (void *)d->idd.res_pass, (void *)d->idd.res_done})
 		if (p) (void)hipFree(p);
 	for (double *p : {d->d_lam, d->d_soft_sym, d->d_soft_bit})
 		if (p) (void)hipFree(p);
@@ -1272,7 +1288,10 @@ extern "C" nbl_status nbl_set_demodulator_ex(nbl_decoder *d, const nbl_demod_des
 	// the channel's buffers are sized per lane of dm_L symbols and the jump table is per symbol position: both are rebuilt for
 	// the new L by the next channel call
 	if (d->d_jump) { (void)hipFree(d->d_jump); d->d_jump = nullptr; }
+	if (d->d_jump_f) { (void)hipFree(d->d_jump_f); d->d_jump_f = nullptr; }
+	d->jump_f_pos = 0;
 	d->noise_cap = 0;
+	d->noise_pos = 0;
 	d->dm_general = general;
 	d->dm_metric = metric;
 	d->dm_order = M;
@@ -1285,10 +1304,12 @@ extern "C" nbl_status nbl_set_demodulator(nbl_decoder *d, const nbl_demod_desc *
 // received samples -> L_ch in the workspace: the BPSK / q-ary kernel, or the general one where nbl_set_demodulator_ex chose it
 // d_prior [B][N p] (may be NULL): the prior-aware instance of the general kernel; the BPSK / q-ary kernels have no foreign position, a
 // prior is inert there
-static hipError_t launch_demod(nbl_decoder *d, const double *d_rx, double sigma, int B, const double *d_prior = nullptr)
+// d_gain [B][L][2] (may be NULL): the gain-aware instances of either kernel
+static hipError_t launch_demod(nbl_decoder *d, const double *d_rx, double sigma, int B, const double *d_prior = nullptr, const double *d_gain = nullptr)
 {
-	if (d->dm_general) return nbl_launch_demod_general(d_rx, d->dm_L, sigma, d->dm_order, d->dm_metric, d->d_cons, d->d_dmdesc, d->g, d->w, B, d->stream, d_prior, d->d_tinv);
-	return nbl_launch_demod(d_rx, d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream);
+	if (d->dm_general)
+		return nbl_launch_demod_general(d_rx, d->dm_L, sigma, d->dm_order, d->dm_metric, d->d_cons, d->d_dmdesc, d->g, d->w, B, d->stream, d_prior, d->d_tinv, d_gain);
+	return nbl_launch_demod(d_rx, d->dm_L, sigma, d->dm_order, d->d_cons, d->d_src, d->g, d->w, B, d->stream, d_gain);
 }
 
 static nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_t st);
@@ -1307,12 +1328,36 @@ static nbl_status stage_rx(nbl_decoder *d, const double *rx, int B)
 		d->d_rx_cap = bytes;
 	}
 	HIP_TRY(d, hipMemcpyAsync(d->d_rx, rx, bytes, hipMemcpyHostToDevice, d->stream));
+	d->rx_gain = false;
 	return NBL_OK;
 }
 
-// nbl_decode_batch_samples, and with a prior nbl_decode_batch_samples_prior
+// a gain buffer grown on demand; its capacity is counted in nbl_workspace_bytes (the slots' are grown on the channel thread: each has
+// its own counter, nothing shared is touched)
+static nbl_status grow_gain(std::string &err, double **buf, size_t *cap, size_t bytes)
+{
+	if (bytes <= *cap) return NBL_OK;
+	if (*buf) (void)hipFree(*buf);
+	*buf = nullptr;
+	*cap = 0;
+	HIP_TRY_E(err, hipMalloc((void **)buf, bytes));
+	*cap = bytes;
+	return NBL_OK;
+}
+
+// host gains [B][L][2] -> d_gain, on the decoder's stream
+static nbl_status stage_gain(nbl_decoder *d, const double *gain, int B)
+{
+	const size_t bytes = (size_t)B * d->dm_L * 16;
+	if (nbl_status s = grow_gain(d->err, &d->d_gain, &d->d_gain_cap, bytes)) return s;
+	HIP_TRY(d, hipMemcpyAsync(d->d_gain, gain, bytes, hipMemcpyHostToDevice, d->stream));
+	d->rx_gain = true;
+	return NBL_OK;
+}
+
+// nbl_decode_batch_samples, with a prior nbl_decode_batch_samples_prior, with gains nbl_decode_batch_samples_csi
 static nbl_status decode_samples(nbl_decoder *d, const double *rx, const double *prior, double sigma, int32_t B, int32_t *out_sym,
-                                 uint8_t *converged, int32_t *iters)
+                                 uint8_t *converged, int32_t *iters, const double *gain = nullptr)
 {
 	if (!d || !rx || !out_sym || B < 0 || !(sigma > 0)) return NBL_ERR_ARG;
 	if (!d->dm_order) { d->err = "nbl_set_demodulator has not been called"; return NBL_ERR_ARG; }
@@ -1322,13 +1367,15 @@ static nbl_status decode_samples(nbl_decoder *d, const double *rx, const double 
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
 	if ((s = stage_rx(d, rx, B))) return s;
+	if (gain && (s = stage_gain(d, gain, B))) return s;
+	const double *d_gain = gain ? d->d_gain : nullptr;
 	if (prior && d->dm_general) {
 		const size_t pbytes = (size_t)B * d->g.N * d->g.p * 8;
 		if ((s = grow_staging(d, &d->d_prior, &d->d_prior_cap, pbytes))) return s;
 		HIP_TRY(d, hipMemcpyAsync(d->d_prior, prior, pbytes, hipMemcpyHostToDevice, d->stream));
-		HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B, d->d_prior));
+		HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B, d->d_prior, d_gain));
 	} else {
-		HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B));
+		HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B, nullptr, d_gain));
 	}
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
@@ -1348,6 +1395,12 @@ extern "C" nbl_status nbl_decode_batch_samples_prior(nbl_decoder *d, const doubl
                                                      int32_t *out_sym, uint8_t *converged, int32_t *iters)
 {
 	return decode_samples(d, rx, prior, sigma, B, out_sym, converged, iters);
+}
+
+extern "C" nbl_status nbl_decode_batch_samples_csi(nbl_decoder *d, const double *rx, const double *gain, const double *prior, double sigma, int32_t B,
+                                                   int32_t *out_sym, uint8_t *converged, int32_t *iters)
+{
+	return decode_samples(d, rx, prior, sigma, B, out_sym, converged, iters, gain);
 }
 
 // ---- bit-LLR input and batched soft output (nbl_soft.hip) ------------------------------------------------
@@ -1509,7 +1562,8 @@ static nbl_status idd_check(nbl_decoder *d, const char *who, const nbl_idd_param
 
 // passes 1 .. idd->passes over the samples d_rx0 [B][L][2] (only ever read); leaves out / converged / iters / pass of every codeword at
 // its batch position in d->idd.res_*.  One stream synchronisation per pass that has a successor: the survivor count sizes the next grids.
-static nbl_status run_idd(nbl_decoder *d, const double *d_rx0, double sigma, int B, const nbl_idd_params *idd)
+// d_gain0 [B][L][2] (may be NULL): the gains of those samples; the survivors' rows are gathered with their samples.
+static nbl_status run_idd(nbl_decoder *d, const double *d_rx0, double sigma, int B, const nbl_idd_params *idd, const double *d_gain0 = nullptr)
 {
 	nbl_decoder::Idd &x = d->idd;
 	const int N = d->g.N, Np = d->g.N * d->g.p, rx_row = 2 * d->dm_L;
@@ -1518,11 +1572,11 @@ static nbl_status run_idd(nbl_decoder *d, const double *d_rx0, double sigma, int
 	if ((s = grow_staging(d, &x.res_iters, &x.iters_cap, (size_t)B * 4))) return s;
 	if ((s = grow_staging(d, &x.res_pass, &x.pass_cap, (size_t)B * 4))) return s;
 	if ((s = grow_staging(d, &x.res_done, &x.done_cap, (size_t)B))) return s;
-	const double *rx = d_rx0, *prior = nullptr;
+	const double *rx = d_rx0, *prior = nullptr, *gain = d_gain0;
 	const int *idx = nullptr;
 	int n = B, side = 0;
 	for (int k = 1;; k++) {
-		HIP_TRY(d, launch_demod(d, rx, sigma, n, prior));
+		HIP_TRY(d, launch_demod(d, rx, sigma, n, prior, gain));
 		if ((s = run_iterations(d, nullptr, n, d->stream))) return s;
 		HIP_TRY(d, nbl_launch_idd_scatter(d->w.out, d->w.done, d->w.iters, idx, n, N, k, x.res_out, x.res_done, x.res_iters, x.res_pass, d->stream));
 		if (k == idd->passes) break;
@@ -1537,8 +1591,11 @@ static nbl_status run_idd(nbl_decoder *d, const double *d_rx0, double sigma, int
 		if ((s = grow_staging(d, &x.rx[side], &x.rx_cap[side], (size_t)live * rx_row * 8))) return s;
 		if ((s = grow_staging(d, &x.idx[side], &x.idx_cap[side], (size_t)live * 4))) return s;
 		HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), n, idd->soft_metric, nullptr, x.ext, d->stream, true));
-		HIP_TRY(d, nbl_launch_idd_gather(d->d_active, live, rx, rx_row, x.ext, Np, idx, x.rx[side], x.prior, x.idx[side], d->stream));
+		if (gain && (s = grow_staging(d, &x.gain[side], &x.gain_cap[side], (size_t)live * rx_row * 8))) return s;
+		HIP_TRY(d, nbl_launch_idd_gather(d->d_active, live, rx, rx_row, x.ext, Np, idx, x.rx[side], x.prior, x.idx[side], d->stream, gain,
+		                                 gain ? x.gain[side] : nullptr));
 		rx = x.rx[side];
+		if (gain) gain = x.gain[side];
 		idx = x.idx[side];
 		prior = x.prior;
 		side ^= 1;
@@ -1556,17 +1613,18 @@ static void idd_inert_passes(const nbl_idd_params *idd, const uint8_t *conv, int
 		for (int b = 0; b < B; b++) passes_used[b] = conv[b] ? 1 : idd->passes;
 }
 
-extern "C" nbl_status nbl_decode_batch_samples_idd(nbl_decoder *d, const double *rx, double sigma, int32_t B, const nbl_idd_params *idd,
-                                                   int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used)
+// nbl_decode_batch_samples_idd, with gains nbl_decode_batch_samples_idd_csi
+static nbl_status decode_samples_idd(nbl_decoder *d, const char *who, const double *rx, const double *gain, double sigma, int32_t B,
+                                     const nbl_idd_params *idd, int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used)
 {
 	if (!d || !rx || !out_sym || B < 0 || !(sigma > 0)) return NBL_ERR_ARG;
-	nbl_status s = idd_check(d, "nbl_decode_batch_samples_idd", idd);
+	nbl_status s = idd_check(d, who, idd);
 	if (s) return s;
 	if (B == 0) return NBL_OK;
 	if (idd->passes == 1 || !d->dm_general) {
 		std::vector<uint8_t> conv(converged ? 0 : (size_t)B);
 		uint8_t *cv = converged ? converged : conv.data();
-		if ((s = decode_samples(d, rx, nullptr, sigma, B, out_sym, cv, iters))) return s;
+		if ((s = decode_samples(d, rx, nullptr, sigma, B, out_sym, cv, iters, gain))) return s;
 		idd_inert_passes(idd, cv, B, passes_used);
 		return NBL_OK;
 	}
@@ -1574,13 +1632,28 @@ extern "C" nbl_status nbl_decode_batch_samples_idd(nbl_decoder *d, const double 
 	HIP_TRY(d, hipSetDevice(d->device));
 	if ((s = ensure_workspace(d, B))) return s;
 	if ((s = stage_rx(d, rx, B))) return s;
-	if ((s = run_idd(d, d->d_rx, sigma, B, idd))) return s;
+	if (gain && (s = stage_gain(d, gain, B))) return s;
+	if ((s = run_idd(d, d->d_rx, sigma, B, idd, gain ? d->d_gain : nullptr))) return s;
 	HIP_TRY(d, hipMemcpyAsync(out_sym, d->idd.res_out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
 	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->idd.res_done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
 	if (iters) HIP_TRY(d, hipMemcpyAsync(iters, d->idd.res_iters, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
 	if (passes_used) HIP_TRY(d, hipMemcpyAsync(passes_used, d->idd.res_pass, (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(d, hipStreamSynchronize(d->stream));
 	return NBL_OK;
+}
+
+extern "C" nbl_status nbl_decode_batch_samples_idd(nbl_decoder *d, const double *rx, double sigma, int32_t B, const nbl_idd_params *idd,
+                                                   int32_t *out_sym, uint8_t *converged, int32_t *iters, int32_t *passes_used)
+{
+	return decode_samples_idd(d, "nbl_decode_batch_samples_idd", rx, nullptr, sigma, B, idd, out_sym, converged, iters, passes_used);
+}
+
+extern "C" nbl_status nbl_decode_batch_samples_idd_csi(nbl_decoder *d, const double *rx, const double *gain, double sigma, int32_t B,
+                                                       const nbl_idd_params *idd, int32_t *out_sym, uint8_t *converged, int32_t *iters,
+                                                       int32_t *passes_used)
+{
+	return decode_samples_idd(d, gain ? "nbl_decode_batch_samples_idd_csi" : "nbl_decode_batch_samples_idd", rx, gain, sigma, B, idd, out_sym,
+	                          converged, iters, passes_used);
 }
 
 // ---- AWGN channel + CRand on the device ------------------------------------------------------------------
@@ -1602,21 +1675,44 @@ extern "C" void nbl_rand_advance(uint32_t state[3], uint64_t draws)
 	state[2] = (uint32_t)((uint64_t)(state[2] % 63599u) * mod_pow(252, draws, 63599) % 63599u);
 }
 
+// A^(4 k) mod m for k < npos, [3][npos]: the state in front of position k of a frame, as a factor on the lane's state
+static std::vector<uint32_t> jump_table(size_t npos)
+{
+	std::vector<uint32_t> jump(3 * npos);
+	const uint32_t A[3] = {249, 251, 252}, M[3] = {61967, 63443, 63599};
+	for (int g = 0; g < 3; g++) {
+		uint64_t x = 1;
+		const uint32_t a4 = mod_pow(A[g], 4, M[g]);
+		for (size_t s = 0; s < npos; s++) { jump[g * npos + s] = (uint32_t)x; x = x * a4 % M[g]; }
+	}
+	return jump;
+}
+
+// nblk of the fading frame at the current L (0 without fading): the frame has nblk + L positions of four uniform draws
+static int fading_blocks(const nbl_decoder *d)
+{
+	return d->fade_model == NBL_FADING_RAYLEIGH ? (d->dm_L + d->fade_coh - 1) / d->fade_coh : 0;
+}
+
 static nbl_status ensure_noise(nbl_decoder *d, int B, std::string &err)
 {
-	const size_t L = d->dm_L;
-	if (!d->d_jump) {
-		std::vector<uint32_t> jump(3 * L);
-		const uint32_t A[3] = {249, 251, 252}, M[3] = {61967, 63443, 63599};
-		for (int g = 0; g < 3; g++) {
-			uint64_t x = 1;
-			const uint32_t a4 = mod_pow(A[g], 4, M[g]);
-			for (size_t s = 0; s < L; s++) { jump[g * L + s] = (uint32_t)x; x = x * a4 % M[g]; }
-		}
+	const size_t nblk = (size_t)fading_blocks(d);
+	const size_t L = (size_t)d->dm_L + nblk; // positions per lane: the buffers below are per position
+	if (nblk && (!d->d_jump_f || d->jump_f_pos != (int)L)) { // the table of the fading frame, beside the AWGN one
+		if (d->d_jump_f) (void)hipFree(d->d_jump_f);
+		d->d_jump_f = nullptr;
+		d->jump_f_pos = 0;
+		const std::vector<uint32_t> jump = jump_table(L);
+		HIP_TRY_E(err, hipMalloc((void **)&d->d_jump_f, jump.size() * 4));
+		HIP_TRY_E(err, hipMemcpy(d->d_jump_f, jump.data(), jump.size() * 4, hipMemcpyHostToDevice));
+		d->jump_f_pos = (int)L;
+	}
+	if (!nblk && !d->d_jump) {
+		const std::vector<uint32_t> jump = jump_table(L);
 		HIP_TRY_E(err, hipMalloc((void **)&d->d_jump, jump.size() * 4));
 		HIP_TRY_E(err, hipMemcpy(d->d_jump, jump.data(), jump.size() * 4, hipMemcpyHostToDevice));
 	}
-	if ((size_t)B <= d->noise_cap) return NBL_OK; // (capacity in lanes of dm_L symbols; nbl_set_demodulator resets it)
+	if ((size_t)B <= d->noise_cap && L <= d->noise_pos) return NBL_OK; // (capacity in lanes of noise_pos positions; nbl_set_demodulator resets it)
 	for (void *p : {(void *)d->d_state, (void *)d->d_txi, (void *)d->d_fn, (void *)d->d_fidx, (void *)d->d_farg, (void *)d->d_fval})
 		if (p) (void)hipFree(p);
 	for (void *p : {(void *)d->h_fidx, (void *)d->h_farg, (void *)d->h_fval})
@@ -1624,6 +1720,7 @@ static nbl_status ensure_noise(nbl_decoder *d, int B, std::string &err)
 	d->d_state = nullptr; d->d_txi = nullptr; d->d_fn = nullptr; d->d_fidx = nullptr; d->d_farg = d->d_fval = nullptr;
 	d->h_fidx = nullptr; d->h_farg = d->h_fval = nullptr;
 	d->noise_cap = 0;
+	d->noise_pos = 0;
 	const size_t nval = (size_t)B * L * 4; // two functions per normal draw, two draws per symbol
 	if (nval > 0xffffffffull) { err = "nbl_decode_batch_noise: batch * symbols too large for 32-bit value indices"; return NBL_ERR_ARG; }
 	// about 16 % of the values are uncertain (5 % of the logarithms, 11 % of the cosines); room for 30 %
@@ -1638,6 +1735,7 @@ static nbl_status ensure_noise(nbl_decoder *d, int B, std::string &err)
 	HIP_TRY_E(err, hipHostMalloc((void **)&d->h_farg, cap * 8, hipHostMallocDefault));
 	HIP_TRY_E(err, hipHostMalloc((void **)&d->h_fval, cap * 8, hipHostMallocDefault));
 	d->noise_cap = B;
+	d->noise_pos = L;
 	d->flag_cap = cap;
 	return NBL_OK;
 }
@@ -1645,9 +1743,13 @@ static nbl_status ensure_noise(nbl_decoder *d, int B, std::string &err)
 // Forms RX = TX + noise for B lanes in *rx_buf (grown on demand) on stream `st`: the three kernels of nbl_noise.hip with the host's
 // libm in between.  Returns with the samples complete in HBM.
 // tx_index == NULL: the indices are already on the device, in d_txi_dev (nbl_transmit_batch).
+// Under nbl_set_fading(RAYLEIGH) the generate kernel runs over the nblk + L positions of the fading frame and nbl_fading.hip's finish
+// kernel forms RX = h * TX + noise, with the per-sample gains into *gain_buf (grown on demand); *has_gain says which of the two ran.
 static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uint32_t *lane_state, double sigma, int B, hipStream_t st,
-                              double **rx_buf, size_t *rx_cap, std::string &err, const uint8_t *d_txi_dev = nullptr)
+                              double **rx_buf, size_t *rx_cap, double **gain_buf, size_t *gain_cap, bool *has_gain, std::string &err,
+                              const uint8_t *d_txi_dev = nullptr)
 {
+	*has_gain = false;
 	if (!d->dm_order) { err = "nbl_set_demodulator has not been called"; return NBL_ERR_ARG; }
 	if (d->h_cons.empty() || !d->d_cons) { err = "the channel needs the constellation points (nbl_demod_desc.constellation), also for BPSK"; return NBL_ERR_ARG; }
 	nbl_status s = ensure_noise(d, B, err);
@@ -1674,6 +1776,8 @@ static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uin
 		HIP_TRY_E(err, hipMalloc((void **)rx_buf, bytes));
 		*rx_cap = bytes;
 	}
+	const int nblk = fading_blocks(d), npos = (int)L + nblk;
+	if (nblk && (s = grow_gain(err, gain_buf, gain_cap, bytes))) return s;
 	const bool timing = getenv("NBL_CHANNEL_TIMING") != nullptr;
 	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double t0 = now();
@@ -1681,12 +1785,12 @@ static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uin
 	HIP_TRY_E(err, hipMemcpyAsync(d->d_state, lane_state, (size_t)B * 12, hipMemcpyHostToDevice, st));
 	if (tx_index) HIP_TRY_E(err, hipMemcpyAsync(d->d_txi, tx_index, (size_t)B * L, hipMemcpyHostToDevice, st));
 	HIP_TRY_E(err, hipMemsetAsync(d->d_fcount, 0, 4, st));
-	HIP_TRY_E(err, nbl_launch_noise_gen(d->d_state, d->d_jump, (int)L, B, d->d_fn, d->d_fidx, d->d_farg, d->d_fcount, (unsigned)d->flag_cap, st));
+	HIP_TRY_E(err, nbl_launch_noise_gen(d->d_state, nblk ? d->d_jump_f : d->d_jump, npos, B, d->d_fn, d->d_fidx, d->d_farg, d->d_fcount, (unsigned)d->flag_cap, st));
 	unsigned nflag = 0;
 	HIP_TRY_E(err, hipMemcpyAsync(&nflag, d->d_fcount, 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY_E(err, hipStreamSynchronize(st));
 	if (nflag > d->flag_cap) { err = "nbl_decode_batch_noise: more uncertain values than the list holds (30 % of all)"; return NBL_ERR_NOMEM; }
-	d->last_flag_frac = (double)nflag / ((double)B * L * 4);
+	d->last_flag_frac = (double)nflag / ((double)B * npos * 4);
 	t1 = now();
 	if (nflag) {
 		HIP_TRY_E(err, hipMemcpyAsync(d->h_farg, d->d_farg, (size_t)nflag * 8, hipMemcpyDeviceToHost, st));
@@ -1715,8 +1819,12 @@ static nbl_status run_channel(nbl_decoder *d, const uint8_t *tx_index, const uin
 		HIP_TRY_E(err, hipMemcpyAsync(d->d_fval, d->h_fval, (size_t)nflag * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY_E(err, nbl_launch_noise_patch(d->d_fn, d->d_fidx, d->d_fval, nflag, st));
 	}
-	HIP_TRY_E(err, nbl_launch_noise_finish(d->d_fn, tx_index ? d->d_txi : d_txi_dev, d->d_cons, sigma, (int)L, B, *rx_buf, st));
+	if (nblk)
+		HIP_TRY_E(err, nbl_launch_fading_finish(d->d_fn, tx_index ? d->d_txi : d_txi_dev, d->d_cons, sigma, (int)L, nblk, d->fade_coh, B, *rx_buf, *gain_buf, st));
+	else
+		HIP_TRY_E(err, nbl_launch_noise_finish(d->d_fn, tx_index ? d->d_txi : d_txi_dev, d->d_cons, sigma, (int)L, B, *rx_buf, st));
 	HIP_TRY_E(err, hipStreamSynchronize(st));
+	*has_gain = nblk != 0;
 	if (timing)
 		fprintf(stderr, "[channel] B=%d: generate %.2f ms, list to host %.2f ms, host libm (%u values) %.2f ms, patch + finish %.2f ms\n", B,
 		        (t1 - t0) * 1e3, (t2 - t1) * 1e3, nflag, (t3 - t2) * 1e3, (now() - t3) * 1e3);
@@ -1732,8 +1840,8 @@ extern "C" nbl_status nbl_decode_batch_noise(nbl_decoder *d, const uint8_t *tx_i
 	HIP_TRY(d, hipSetDevice(d->device));
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
-	if ((s = run_channel(d, tx_index, lane_state, sigma, B, d->stream, &d->d_rx, &d->d_rx_cap, d->err))) return s;
-	HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B));
+	if ((s = run_channel(d, tx_index, lane_state, sigma, B, d->stream, &d->d_rx, &d->d_rx_cap, &d->d_gain, &d->d_gain_cap, &d->rx_gain, d->err))) return s;
+	HIP_TRY(d, launch_demod(d, d->d_rx, sigma, B, nullptr, d->rx_gain ? d->d_gain : nullptr));
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
 	if (converged) HIP_TRY(d, hipMemcpyAsync(converged, d->w.done, (size_t)B, hipMemcpyDeviceToHost, d->stream));
@@ -1750,7 +1858,8 @@ extern "C" nbl_status nbl_channel_batch(nbl_decoder *d, int32_t slot, const uint
 	HIP_TRY_E(d->err2, hipSetDevice(d->device));
 	if (!d->stream2) HIP_TRY_E(d->err2, hipStreamCreateWithFlags(&d->stream2, hipStreamNonBlocking));
 	d->rxs_B[slot] = 0;
-	const nbl_status s = run_channel(d, tx_index, lane_state, sigma, B, d->stream2, &d->d_rxs[slot], &d->d_rxs_cap[slot], d->err2);
+	const nbl_status s = run_channel(d, tx_index, lane_state, sigma, B, d->stream2, &d->d_rxs[slot], &d->d_rxs_cap[slot], &d->d_gains[slot],
+	                                 &d->d_gains_cap[slot], &d->slot_gain[slot], d->err2);
 	if (s == NBL_OK) d->rxs_B[slot] = B;
 	return s;
 }
@@ -1783,7 +1892,7 @@ extern "C" nbl_status nbl_decode_batch_resident(nbl_decoder *d, int32_t slot, do
 	HIP_TRY(d, hipSetDevice(d->device));
 	nbl_status s = ensure_workspace(d, B);
 	if (s) return s;
-	HIP_TRY(d, launch_demod(d, d->d_rxs[slot], sigma, B));
+	HIP_TRY(d, launch_demod(d, d->d_rxs[slot], sigma, B, nullptr, d->slot_gain[slot] ? d->d_gains[slot] : nullptr));
 	if (d->tx.on) d->tx.dec_B[slot] = 0;
 	if ((s = run_iterations(d, nullptr, B, d->stream))) return s;
 	if (out_sym) HIP_TRY(d, hipMemcpyAsync(out_sym, d->w.out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
@@ -1816,7 +1925,7 @@ extern "C" nbl_status nbl_decode_batch_resident_idd(nbl_decoder *d, int32_t slot
 	HIP_TRY(d, hipSetDevice(d->device));
 	if ((s = ensure_workspace(d, B))) return s;
 	if (d->tx.on) d->tx.dec_B[slot] = 0;
-	if ((s = run_idd(d, d->d_rxs[slot], sigma, B, idd))) return s; // (the slot's samples are only read)
+	if ((s = run_idd(d, d->d_rxs[slot], sigma, B, idd, d->slot_gain[slot] ? d->d_gains[slot] : nullptr))) return s; // (the slot's samples and gains are only read)
 	if (out_sym) HIP_TRY(d, hipMemcpyAsync(out_sym, d->idd.res_out, (size_t)B * d->g.N * 4, hipMemcpyDeviceToHost, d->stream));
 	if (d->tx.on) { // the slot keeps the final words for nbl_count_errors
 		if ((s = ensure_slot_dec(d, slot, B))) return s;
@@ -1833,7 +1942,9 @@ extern "C" nbl_status nbl_decode_batch_resident_idd(nbl_decoder *d, int32_t slot
 // Diagnostic only (not part of include/nbldpc.h): device time in milliseconds of ONE launch of the demodulator on the samples a slot
 // holds, between two events on the decoder's stream -- with_prior != 0: the prior-aware instance, on an all-zero prior (the kernel's
 // work does not depend on the values).  For tools/idd_pass.py.
-extern "C" nbl_status nbl_debug_time_demod(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t with_prior, double *ms)
+// with_gain != 0 (nbl_debug_time_demod_csi): the gain-aware instance, on the slot's own gains where it holds some, else on all-zero
+// gains (the kernel's work does not depend on the values).  For tools/fading_fer.py.
+static nbl_status time_demod(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t with_prior, int32_t with_gain, double *ms)
 {
 	if (!d || !ms || B <= 0 || slot < 0 || slot > 1 || !(sigma > 0) || !d->dm_order || d->rxs_B[slot] != B) return NBL_ERR_ARG;
 	d->err.clear();
@@ -1847,11 +1958,20 @@ extern "C" nbl_status nbl_debug_time_demod(nbl_decoder *d, int32_t slot, double 
 		HIP_TRY(d, hipMemsetAsync(d->d_prior, 0, pbytes, d->stream));
 		prior = d->d_prior;
 	}
+	const double *gain = nullptr;
+	if (with_gain && d->slot_gain[slot]) gain = d->d_gains[slot];
+	else if (with_gain) {
+		const size_t gbytes = (size_t)B * d->dm_L * 16;
+		if ((s = grow_gain(d->err, &d->d_gain, &d->d_gain_cap, gbytes))) return s;
+		HIP_TRY(d, hipMemsetAsync(d->d_gain, 0, gbytes, d->stream));
+		d->rx_gain = false;
+		gain = d->d_gain;
+	}
 	hipEvent_t a = nullptr, b = nullptr;
 	HIP_TRY(d, hipEventCreate(&a));
 	HIP_TRY(d, hipEventCreate(&b));
 	hipError_t e = hipEventRecord(a, d->stream);
-	if (e == hipSuccess) e = launch_demod(d, d->d_rxs[slot], sigma, B, prior);
+	if (e == hipSuccess) e = launch_demod(d, d->d_rxs[slot], sigma, B, prior, gain);
 	if (e == hipSuccess) e = hipEventRecord(b, d->stream);
 	if (e == hipSuccess) e = hipEventSynchronize(b);
 	float t = 0;
@@ -1863,6 +1983,52 @@ extern "C" nbl_status nbl_debug_time_demod(nbl_decoder *d, int32_t slot, double 
 	return NBL_OK;
 }
 
+extern "C" nbl_status nbl_debug_time_demod(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t with_prior, double *ms)
+{
+	return time_demod(d, slot, sigma, B, with_prior, 0, ms);
+}
+
+extern "C" nbl_status nbl_debug_time_demod_csi(nbl_decoder *d, int32_t slot, double sigma, int32_t B, int32_t with_prior, int32_t with_gain, double *ms)
+{
+	return time_demod(d, slot, sigma, B, with_prior, with_gain, ms);
+}
+
+// ---- flat fading (include/nbldpc.h) ---------------------------------------------------------------------------
+
+extern "C" nbl_status nbl_set_fading(nbl_decoder *d, const nbl_fading_desc *f)
+{
+	if (!d) return NBL_ERR_ARG;
+	if (!f || f->model == NBL_FADING_NONE) { d->fade_model = NBL_FADING_NONE; d->fade_coh = 1; return NBL_OK; }
+	if (f->model != NBL_FADING_RAYLEIGH) {
+		d->err = "nbl_set_fading: unknown model " + std::to_string(f->model) + " (NBL_FADING_NONE = 0, NBL_FADING_RAYLEIGH = 1)";
+		return NBL_ERR_ARG;
+	}
+	if (f->coherence < 1) {
+		d->err = "nbl_set_fading: coherence must be at least 1, got " + std::to_string(f->coherence);
+		return NBL_ERR_ARG;
+	}
+	d->fade_model = f->model;
+	d->fade_coh = f->coherence;
+	return NBL_OK;
+}
+
+extern "C" uint64_t nbl_channel_draws(const nbl_decoder *d)
+{
+	return d ? 4ull * (uint64_t)fading_blocks(d) + 4ull * (uint64_t)d->dm_L : 0;
+}
+
+extern "C" nbl_status nbl_read_gains(nbl_decoder *d, int32_t slot, int32_t b0, int32_t n, double *gain)
+{
+	if (!d || slot < 0 || slot > 1 || b0 < 0 || n < 0 || (n > 0 && !gain)) return NBL_ERR_ARG;
+	d->err.clear();
+	if (d->rxs_B[slot] <= 0 || !d->slot_gain[slot]) { d->err = "nbl_read_gains: the slot holds no gains (its samples were not formed under nbl_set_fading)"; return NBL_ERR_ARG; }
+	if ((long long)b0 + n > d->rxs_B[slot]) { d->err = "nbl_read_gains: the slot does not hold these lanes"; return NBL_ERR_ARG; }
+	if (n == 0) return NBL_OK;
+	HIP_TRY(d, hipSetDevice(d->device));
+	HIP_TRY(d, hipMemcpy(gain, d->d_gains[slot] + (size_t)b0 * d->dm_L * 2, (size_t)n * d->dm_L * 16, hipMemcpyDeviceToHost));
+	return NBL_OK;
+}
+
 // Diagnostic only (not part of include/nbldpc.h): run the channel alone and return the received samples [B][L][2] and the
 // fraction of log / cos values that went to the host's libm.
 extern "C" nbl_status nbl_debug_channel(nbl_decoder *d, const uint8_t *tx_index, const uint32_t *lane_state, double sigma, int32_t B,
@@ -1871,7 +2037,7 @@ extern "C" nbl_status nbl_debug_channel(nbl_decoder *d, const uint8_t *tx_index,
 	if (!d || !tx_index || !lane_state || !rx_out || B <= 0) return NBL_ERR_ARG;
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
-	nbl_status s = run_channel(d, tx_index, lane_state, sigma, B, d->stream, &d->d_rx, &d->d_rx_cap, d->err);
+	nbl_status s = run_channel(d, tx_index, lane_state, sigma, B, d->stream, &d->d_rx, &d->d_rx_cap, &d->d_gain, &d->d_gain_cap, &d->rx_gain, d->err);
 	if (s) return s;
 	HIP_TRY(d, hipMemcpyAsync(rx_out, d->d_rx, (size_t)B * d->dm_L * 16, hipMemcpyDeviceToHost, d->stream));
 	HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -2177,7 +2343,8 @@ extern "C" nbl_status nbl_transmit_batch(nbl_decoder *d, int32_t slot, const uin
 		HIP_TRY_E(d->err2, hipMemsetAsync(t.bits, 0, (size_t)B * rows, st)); // all-zero message and code word, encoder skipped (Comm.cpp:258-268)
 	}
 	HIP_TRY_E(d->err2, nbl_launch_tx_pack(t.bits, t.keep, N, p, d->dm_L, t.mb, B, t.code[slot], t.txi[slot], st));
-	s = run_channel(d, nullptr, lane_state, sigma, B, st, &d->d_rxs[slot], &d->d_rxs_cap[slot], d->err2, t.txi[slot]);
+	s = run_channel(d, nullptr, lane_state, sigma, B, st, &d->d_rxs[slot], &d->d_rxs_cap[slot], &d->d_gains[slot], &d->d_gains_cap[slot],
+	                &d->slot_gain[slot], d->err2, t.txi[slot]);
 	if (s == NBL_OK) { d->rxs_B[slot] = B; t.tx_B[slot] = B; }
 	return s;
 }

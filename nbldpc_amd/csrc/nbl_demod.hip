@@ -15,6 +15,11 @@
 // The at most m prior values of a point are the same for the whole wave: codeword, point and the claim table tinv[s m + i] are made
 // provably uniform, so they arrive as scalar loads, not as 64 lanes reading one address.  The instance without PRIOR is the kernel
 // the prior-less calls have always launched.
+//
+// GAIN (nbl_decode_batch_samples_csi, the resident decodes under nbl_set_fading): step 1 measures the distance to
+// the FADED point (hr cr - hi ci, hr ci + hi cr), (hr, hi) = gain[b][s].  The gain of a point is the same for the whole wave: codeword
+// and point are made provably uniform, as for the priors, so it arrives as one scalar load.  The instances without GAIN are the
+// kernels the gain-less calls have always launched.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/nbldpc.h"
@@ -53,11 +58,11 @@ __device__ __forceinline__ int demod_pattern_of_value(const NblDemodPoint &pt, i
 	return pat;
 }
 
-template <bool PRIOR>
+template <bool PRIOR, bool GAIN>
 __global__ __launch_bounds__(256) void demod_general_kernel(const double *__restrict__ rx, int L, double sigma_n, int M, int m, int metric,
                                                             const double *__restrict__ cons, const NblDemodPoint *__restrict__ desc,
                                                             NblGraphDev g, NblWork w, int B, const double *__restrict__ prior,
-                                                            const int *__restrict__ tinv)
+                                                            const int *__restrict__ tinv, const double *__restrict__ gain)
 {
 	__shared__ double lds[4][512];
 	const int lane = lane_id();
@@ -94,9 +99,20 @@ __global__ __launch_bounds__(256) void demod_general_kernel(const double *__rest
 					if (gb >= 0) { pv[i] = pr[gb]; cm |= 1 << i; }
 				}
 		}
+		double hr = 0.0, hi = 0.0;
+		if constexpr (GAIN) {
+			const double *gn = gain + ((size_t)uniform(b) * L + (size_t)uniform(pt.s)) * 2;
+			hr = gn[0];
+			hi = gn[1];
+		}
 		DSYNC(); // the previous point's table has been read by every lane
 		for (int c = lane; c < M; c += 64) {
-			const double cr = cons[2 * c], ci = cons[2 * c + 1];
+			double cr = cons[2 * c], ci = cons[2 * c + 1];
+			if constexpr (GAIN) {
+				const double pr = hr * cr - hi * ci, pi = hr * ci + hi * cr;
+				cr = pr;
+				ci = pi;
+			}
 			double d = (re - cr) * (re - cr) + (im - ci) * (im - ci);
 			if constexpr (PRIOR) {
 				double A = 0.0;
@@ -146,18 +162,21 @@ __global__ __launch_bounds__(256) void demod_general_kernel(const double *__rest
 
 hipError_t nbl_launch_demod_general(const double *d_rx, int L, double sigma, int mod_order, int metric, const double *d_cons,
                                     const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st,
-                                    const double *d_prior, const int *d_tinv)
+                                    const double *d_prior, const int *d_tinv, const double *d_gain)
 {
 	int m = 0;
 	while ((1 << m) < mod_order) m++;
 	if (m < 1 || m > 8 || (1 << m) != mod_order || g.q > 256 || !d_cons || !d_desc) return hipErrorInvalidValue;
 	long long nodes = (long long)B * g.N;
 	dim3 grid((unsigned)((nodes + 3) / 4)), block(256);
-	if (d_prior) {
-		if (!d_tinv) return hipErrorInvalidValue;
-		demod_general_kernel<true><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, d_prior, d_tinv);
-	} else {
-		demod_general_kernel<false><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, nullptr, nullptr);
-	}
+	if (d_prior && !d_tinv) return hipErrorInvalidValue;
+	if (d_prior && d_gain)
+		demod_general_kernel<true, true><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, d_prior, d_tinv, d_gain);
+	else if (d_gain)
+		demod_general_kernel<false, true><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, nullptr, nullptr, d_gain);
+	else if (d_prior)
+		demod_general_kernel<true, false><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, d_prior, d_tinv, nullptr);
+	else
+		demod_general_kernel<false, false><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, m, metric, d_cons, d_desc, g, w, B, nullptr, nullptr, nullptr);
 	return hipGetLastError();
 }

@@ -6,7 +6,8 @@
 //   idd_gather_kernel    before the next pass: for the i-th entry j of the active list (the rows that did not converge, ascending),
 //                        the samples, the extrinsic bit LLRs (the next prior) and the batch position of row j into row i of the next
 //                        pass's buffers.  Source and destination never alias: the samples ping-pong between two buffers and the
-//                        caller's (or a slot's) samples are only ever read.
+//                        caller's (or a slot's) samples are only ever read.  GAIN (nbl_decode_batch_samples_idd_csi, a slot with
+//                        gains): the survivors' channel gains, rows of the samples' length, travel with their samples.
 // Both are flat grid-stride copies: consecutive lanes take consecutive elements of a row.
 #include <hip/hip_runtime.h>
 #include "nbl_device.h"
@@ -29,17 +30,20 @@ __global__ __launch_bounds__(256) void idd_scatter_kernel(const int *__restrict_
 	}
 }
 
+template <bool GAIN>
 __global__ __launch_bounds__(256) void idd_gather_kernel(const int *__restrict__ active, int n, const double *__restrict__ rx_src, int rx_row,
                                                          const double *__restrict__ ext_src, int prior_row, const int *__restrict__ idx_src,
-                                                         double *__restrict__ rx_dst, double *__restrict__ prior_dst, int *__restrict__ idx_dst)
+                                                         double *__restrict__ rx_dst, double *__restrict__ prior_dst, int *__restrict__ idx_dst,
+                                                         const double *__restrict__ gain_src, double *__restrict__ gain_dst)
 {
-	const int row = rx_row + prior_row;
+	const int row = rx_row + prior_row + (GAIN ? rx_row : 0);
 	const long long total = (long long)n * row;
 	for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
 		const int i = (int)(e / row), k = (int)(e % row);
 		const int j = active[i];
 		if (k < rx_row) rx_dst[(size_t)i * rx_row + k] = rx_src[(size_t)j * rx_row + k];
-		else prior_dst[(size_t)i * prior_row + (k - rx_row)] = ext_src[(size_t)j * prior_row + (k - rx_row)];
+		else if (k < rx_row + prior_row) prior_dst[(size_t)i * prior_row + (k - rx_row)] = ext_src[(size_t)j * prior_row + (k - rx_row)];
+		else if constexpr (GAIN) gain_dst[(size_t)i * rx_row + (k - rx_row - prior_row)] = gain_src[(size_t)j * rx_row + (k - rx_row - prior_row)];
 		if (k == 0) idx_dst[i] = idx_src ? idx_src[j] : j;
 	}
 }
@@ -61,10 +65,16 @@ hipError_t nbl_launch_idd_scatter(const int *d_out, const uint8_t *d_done, const
 }
 
 hipError_t nbl_launch_idd_gather(const int *d_active, int n, const double *d_rx_src, int rx_row, const double *d_ext_src, int prior_row,
-                                 const int *d_idx_src, double *d_rx_dst, double *d_prior_dst, int *d_idx_dst, hipStream_t st)
+                                 const int *d_idx_src, double *d_rx_dst, double *d_prior_dst, int *d_idx_dst, hipStream_t st,
+                                 const double *d_gain_src, double *d_gain_dst)
 {
 	if (n < 1 || rx_row < 1 || prior_row < 1 || !d_active || !d_rx_src || !d_ext_src || !d_rx_dst || !d_prior_dst || !d_idx_dst) return hipErrorInvalidValue;
-	idd_gather_kernel<<<dim3(idd_blocks((long long)n * (rx_row + prior_row))), dim3(256), 0, st>>>(d_active, n, d_rx_src, rx_row, d_ext_src, prior_row,
-	                                                                                                d_idx_src, d_rx_dst, d_prior_dst, d_idx_dst);
+	if ((d_gain_src == nullptr) != (d_gain_dst == nullptr)) return hipErrorInvalidValue;
+	if (d_gain_src)
+		idd_gather_kernel<true><<<dim3(idd_blocks((long long)n * (2 * rx_row + prior_row))), dim3(256), 0, st>>>(
+		    d_active, n, d_rx_src, rx_row, d_ext_src, prior_row, d_idx_src, d_rx_dst, d_prior_dst, d_idx_dst, d_gain_src, d_gain_dst);
+	else
+		idd_gather_kernel<false><<<dim3(idd_blocks((long long)n * (rx_row + prior_row))), dim3(256), 0, st>>>(
+		    d_active, n, d_rx_src, rx_row, d_ext_src, prior_row, d_idx_src, d_rx_dst, d_prior_dst, d_idx_dst, nullptr, nullptr);
 	return hipGetLastError();
 }

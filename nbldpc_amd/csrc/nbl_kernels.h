@@ -6,11 +6,13 @@
 
 hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblWork &w, int B, int write_v2c, hipStream_t st);
 hipError_t nbl_launch_demod(const double *d_rx, int L, double sigma, int mod_order, const double *d_cons, const int *d_src,
-                            const NblGraphDev &g, const NblWork &w, int B, hipStream_t st);
+                            const NblGraphDev &g, const NblWork &w, int B, hipStream_t st,
+                            const double *d_gain = nullptr /* [B][L][2]: the gain-aware instance */);
 // general demodulator, any mod_order = 2^m <= 256 (nbl_demod.hip); metric: NBL_DEMOD_* of include/nbldpc.h
 hipError_t nbl_launch_demod_general(const double *d_rx, int L, double sigma, int mod_order, int metric, const double *d_cons,
                                     const NblDemodPoint *d_desc, const NblGraphDev &g, const NblWork &w, int B, hipStream_t st,
-                                    const double *d_prior = nullptr /* [B][N p]: the prior-aware instance */, const int *d_tinv = nullptr);
+                                    const double *d_prior = nullptr /* [B][N p]: the prior-aware instance */, const int *d_tinv = nullptr,
+                                    const double *d_gain = nullptr /* [B][L][2]: the gain-aware instances */);
 hipError_t nbl_launch_vn(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool damp, hipStream_t st);
 hipError_t nbl_launch_syn(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_compact(const uint8_t *done, int B, int *active, int *n_act, hipStream_t st);
@@ -80,13 +82,19 @@ hipError_t nbl_launch_idd_scatter(const int *d_out, const uint8_t *d_done, const
                                   int n, int N, int pass, int *d_res_out, uint8_t *d_res_done, int *d_res_iters, int *d_res_pass, hipStream_t st);
 hipError_t nbl_launch_idd_gather(const int *d_active, int n, const double *d_rx_src, int rx_row, const double *d_ext_src, int prior_row,
                                  const int *d_idx_src /* NULL: the identity */, double *d_rx_dst, double *d_prior_dst, int *d_idx_dst,
-                                 hipStream_t st);
+                                 hipStream_t st, const double *d_gain_src = nullptr /* rows of rx_row doubles, carried like the samples */,
+                                 double *d_gain_dst = nullptr);
 
 // AWGN channel + CRand on the device (nbl_noise.hip)
 hipError_t nbl_launch_noise_gen(const uint32_t *state, const uint32_t *jump, int L, int B, double *fn, uint32_t *flag_idx, double *flag_arg,
                                 unsigned *flag_count, unsigned cap, hipStream_t st);
 hipError_t nbl_launch_noise_patch(double *fn, const uint32_t *flag_idx, const double *val, unsigned n, hipStream_t st);
 hipError_t nbl_launch_noise_finish(const double *fn, const uint8_t *tx_index, const double *cons, double sigma, int L, int B, double *rx, hipStream_t st);
+
+// Rayleigh block fading on the device (nbl_fading.hip): fn [B][npos][2] double2 as nbl_launch_noise_gen leaves it over npos = nblk + L
+// positions (the nblk gain draws first, then the L noise draws); RX = h * TX + noise and the per-sample gains
+hipError_t nbl_launch_fading_finish(const double *fn, const uint8_t *tx_index, const double *cons, double sigma, int L, int nblk, int coherence,
+                                    int B, double *rx, double *gain, hipStream_t st);
 
 // transmit chain and error count on the device (nbl_tx.hip).  T is word-major: T[w * rows + r] = columns 64 w .. 64 w + 63 of row r.
 #define NBL_TX_F 8 // frames a thread of the encode kernel carries (their packed inputs sit in LDS: NBL_TX_F * nw * 8 bytes)

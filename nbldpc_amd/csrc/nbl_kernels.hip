@@ -53,9 +53,13 @@ __global__ void init_kernel(const double *__restrict__ Lin, NblGraphDev g, NblWo
 // soft demodulator: received samples -> symbol LLRs, written straight into the padded Lch layout.
 // Expression order is CComm::Demodulate's (Comm.cpp:356, :364-378 for BPSK; :394-395 for q-ary constellations).
 // ---------------------------------------------------------------------------------------------------------
+// GAIN (include/nbldpc.h, "demodulators with gains"): gain [B][L][2], BPSK takes z = hr re + hi im in place of re,
+// the q-ary path the faded points of its sample in place of the table's.  The instance without GAIN is the kernel the gain-less calls
+// have always launched.
+template <bool GAIN>
 __global__ __launch_bounds__(256) void demod_kernel(const double *__restrict__ rx, int L, double sigma_n, int mod_order, int p,
                                                     const double *__restrict__ cons, const int *__restrict__ src, NblGraphDev g,
-                                                    NblWork w, int B)
+                                                    NblWork w, int B, const double *__restrict__ gain)
 {
 	const int lane = lane_id();
 	const long long node = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -63,11 +67,17 @@ __global__ __launch_bounds__(256) void demod_kernel(const double *__restrict__ r
 	const int b = (int)(node / g.N), n = (int)(node % g.N), q = g.q;
 	double *dst = w.Lch + ((size_t)b * g.N + n) * q;
 	const double *r = rx + (size_t)b * L * 2;
+	const double *h = GAIN ? gain + (size_t)b * L * 2 : nullptr;
 	if (mod_order == 2) {
 		double bl[8];
 		for (int k = 0; k < 8; k++) {
 			const int sidx = (k < p) ? src[n * p + k] : -1;
-			bl[k] = (sidx < 0) ? 0.0 : -2 * r[2 * sidx] / (sigma_n * sigma_n);
+			if constexpr (GAIN) {
+				const double z = (sidx < 0) ? 0.0 : h[2 * sidx] * r[2 * sidx] + h[2 * sidx + 1] * r[2 * sidx + 1];
+				bl[k] = (sidx < 0) ? 0.0 : -2 * z / (sigma_n * sigma_n);
+			} else {
+				bl[k] = (sidx < 0) ? 0.0 : -2 * r[2 * sidx] / (sigma_n * sigma_n);
+			}
 		}
 		for (int a = lane; a < q; a += 64) {
 			double acc = 0;
@@ -78,10 +88,23 @@ __global__ __launch_bounds__(256) void demod_kernel(const double *__restrict__ r
 		}
 	} else {
 		const int sidx = src[n];
-		const double c0r = cons[0], c0i = cons[1];
+		double c0r = cons[0], c0i = cons[1];
 		const double re = sidx < 0 ? 0.0 : r[2 * sidx], im = sidx < 0 ? 0.0 : r[2 * sidx + 1];
+		double hr = 0.0, hi = 0.0;
+		if constexpr (GAIN) {
+			hr = sidx < 0 ? 0.0 : h[2 * sidx];
+			hi = sidx < 0 ? 0.0 : h[2 * sidx + 1];
+			const double p0r = hr * c0r - hi * c0i, p0i = hr * c0i + hi * c0r;
+			c0r = p0r;
+			c0i = p0i;
+		}
 		for (int a = lane; a < q; a += 64) {
-			const double cr = cons[2 * a], ci = cons[2 * a + 1];
+			double cr = cons[2 * a], ci = cons[2 * a + 1];
+			if constexpr (GAIN) {
+				const double par = hr * cr - hi * ci, pai = hr * ci + hi * cr;
+				cr = par;
+				ci = pai;
+			}
 			const double num = (2 * re - c0r - cr) * (cr - c0r) + (2 * im - c0i - ci) * (ci - c0i);
 			dst[a] = (a == 0 || sidx < 0) ? 0.0 : num / (2 * sigma_n * sigma_n);
 		}
@@ -312,11 +335,12 @@ hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblW
 }
 
 hipError_t nbl_launch_demod(const double *d_rx, int L, double sigma, int mod_order, const double *d_cons, const int *d_src,
-                            const NblGraphDev &g, const NblWork &w, int B, hipStream_t st)
+                            const NblGraphDev &g, const NblWork &w, int B, hipStream_t st, const double *d_gain)
 {
 	long long nodes = (long long)B * g.N;
 	dim3 grid((unsigned)((nodes + 3) / 4)), block(256);
-	demod_kernel<<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, g.p, d_cons, d_src, g, w, B);
+	if (d_gain) demod_kernel<true><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, g.p, d_cons, d_src, g, w, B, d_gain);
+	else demod_kernel<false><<<grid, block, 0, st>>>(d_rx, L, sigma, mod_order, g.p, d_cons, d_src, g, w, B, nullptr);
 	return hipGetLastError();
 }
 

@@ -104,6 +104,100 @@ int nblh_channel(const char *profile, double ebn0, int frames, double *rx, unsig
 	return L;
 }
 
+// nblh_channel over the Rayleigh block-fading channel (CComm::Channel_Rayleigh, `coherence` samples per gain), whatever NBL_CHANNEL
+// says: additionally the per-sample gains gain [frames*P][L][2]; *draws_out = the uniform draws one frame moves a lane's generator.
+int nblh_channel_fading(const char *profile, double ebn0, int frames, int coherence, double *rx, double *gain, unsigned char *tx_index,
+                        unsigned int *state, double *sigma_out, unsigned long long *draws_out)
+{
+	if (coherence < 1) return -4;
+	CSimulation sim;
+	if (sim.Initial(profile) != 0) return -1;
+	sim.EbN0 = ebn0;
+	CLink link;
+	link.sim = sim;
+	CNBLDPC &code = link.code;
+	if (!code.Initial(link.sim, -1)) return -2;
+	const int P = sim.parallel;
+	std::vector<std::unique_ptr<CComm>> lanes;
+	for (int i = 0; i < P; i++) {
+		lanes.emplace_back(new CComm());
+		if (!lanes.back()->Initial(link.sim, i, &code)) return -3;
+		lanes.back()->fade_model = NBL_FADING_RAYLEIGH;
+		lanes.back()->fade_block = coherence;
+		lanes.back()->GAIN.assign(lanes.back()->MOD_SYM_LEN, CComplex());
+		lanes.back()->SetEbN0(link.sim, i);
+	}
+	if (sigma_out) *sigma_out = lanes[0]->sigma_n;
+	if (draws_out) *draws_out = lanes[0]->ChannelDraws();
+	const int L = lanes[0]->MOD_SYM_LEN;
+	auto work = [&](int lo, int hi) {
+		for (int i = lo; i < hi; i++) {
+			CComm &c = *lanes[i];
+			for (int f = 0; f < frames; f++) {
+				const size_t b = (size_t)f * P + i;
+				state[b * 3 + 0] = (unsigned int)(c.Rand.IX % 61967ul);
+				state[b * 3 + 1] = (unsigned int)(c.Rand.IY % 63443ul);
+				state[b * 3 + 2] = (unsigned int)(c.Rand.IZ % 63599ul);
+				c.FrontEndToChannel();
+				for (int s = 0; s < L; s++) {
+					rx[(b * L + s) * 2] = c.RX_MOD_SYM[s].Real;
+					rx[(b * L + s) * 2 + 1] = c.RX_MOD_SYM[s].Image;
+					gain[(b * L + s) * 2] = c.GAIN[s].Real;
+					gain[(b * L + s) * 2 + 1] = c.GAIN[s].Image;
+					tx_index[b * L + s] = c.TX_MOD_IDX[s];
+				}
+			}
+		}
+	};
+	int T = (int)std::thread::hardware_concurrency();
+	if (const char *e = getenv("NBL_HOST_THREADS")) T = atoi(e);
+	if (T > 16) T = 16;
+	if (T > P) T = P;
+	if (T <= 1) work(0, P);
+	else {
+		std::vector<std::thread> th;
+		for (int t = 0; t < T; t++) th.emplace_back(work, (int)((long long)P * t / T), (int)((long long)P * (t + 1) / T));
+		for (auto &x : th) x.join();
+	}
+	return L;
+}
+
+// The host layer's demodulators with gains on B frames (include/nbldpc.h, "demodulators with gains"): rx, gain [B][L][2] -> out
+// [B][N][2^p - 1].  path 0: the general demodulator (src [N p] label-bit indices, prior [B][N p] or NULL, metric NBL_DEMOD_*);
+// path 1: BPSK (src [N p] sample indices); path 2: one point per symbol (src [N] sample indices, M = 2^p).  gain == NULL: the
+// gain-less functions (general path only).  No GPU, no profile.
+int nblh_demod_csi(int path, int N, int p, int M, int L, const double *cons, const int *src, const double *rx, const double *gain,
+                   const double *prior, double sigma, int metric, int B, double *out)
+{
+	if (N <= 0 || p < 1 || p > 8 || L <= 0 || B < 0 || path < 0 || path > 2) return -1;
+	const size_t w = (size_t)(1 << p) - 1;
+	if (path == 0) {
+		if (M < 2 || M > 256 || (M & (M - 1)) || (metric != 0 && metric != 1)) return -1;
+		int m = 0;
+		while ((1 << m) < M) m++;
+		std::vector<char> seen((size_t)L * m, 0);
+		for (int i = 0; i < N * p; i++) {
+			if (src[i] < 0) continue;
+			if (src[i] >= L * m || seen[src[i]]) return -2;
+			seen[src[i]] = 1;
+		}
+		for (int b = 0; b < B; b++)
+			CComm::DemodulateGeneral(N, p, M, L, cons, src, rx + (size_t)b * L * 2, gain ? gain + (size_t)b * L * 2 : nullptr, sigma, metric,
+			                         prior ? prior + (size_t)b * N * p : nullptr, out + (size_t)b * N * w);
+		return 0;
+	}
+	if (!gain) return -1;
+	const int nsrc = path == 1 ? N * p : N;
+	for (int i = 0; i < nsrc; i++)
+		if (src[i] >= L) return -2;
+	if (path == 2 && M != (1 << p)) return -1;
+	for (int b = 0; b < B; b++) {
+		if (path == 1) CComm::DemodulateBpskCsi(N, p, src, rx + (size_t)b * L * 2, gain + (size_t)b * L * 2, sigma, out + (size_t)b * N * w);
+		else CComm::DemodulateQaryCsi(N, 1 << p, cons, src, rx + (size_t)b * L * 2, gain + (size_t)b * L * 2, sigma, out + (size_t)b * N * w);
+	}
+	return 0;
+}
+
 // CComm::DemodulateGeneral on B frames: rx [B][L][2] -> out [B][N][2^p - 1].  No GPU, no profile.
 int nblh_demod_general(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric, int B, double *out)
 {

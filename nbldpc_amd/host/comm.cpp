@@ -69,6 +69,23 @@ bool CComm::Initial(CSimulation &sim, int lane, CNBLDPC *shared)
 		else if (strcmp(e, "logsum")) { error = "NBL_DEMOD_METRIC must be maxlog or logsum"; std::cerr << error << std::endl; return false; }
 	}
 
+	fade_model = NBL_FADING_NONE;
+	fade_block = 1;
+	if (const char *e = getenv("NBL_CHANNEL")) {
+		if (!strcmp(e, "rayleigh")) fade_model = NBL_FADING_RAYLEIGH;
+		else if (strcmp(e, "awgn")) { error = std::string("NBL_CHANNEL=") + e + ": unknown channel (awgn, rayleigh)"; std::cerr << error << std::endl; return false; }
+	}
+	if (const char *e = getenv("NBL_FADE_BLOCK")) {
+		char *end = nullptr;
+		const long k = strtol(e, &end, 10);
+		if (!*e || *end || k < 1 || k > 0x7fffffffl) {
+			error = std::string("NBL_FADE_BLOCK=") + e + ": the number of samples that share one gain must be an integer from 1 up";
+			std::cerr << error << std::endl;
+			return false;
+		}
+		fade_block = (int)k;
+	}
+
 	// constellation file: "Point: i Real: x Imag: y" per line (Comm.cpp:113-126)
 	CONSTELLATION.assign(modOrder, CComplex());
 	std::ifstream fc(sim.ConstellationFileName);
@@ -85,6 +102,7 @@ bool CComm::Initial(CSimulation &sim, int lane, CNBLDPC *shared)
 	TX_MOD_BIT.assign(MOD_BIT_LEN, 0);
 	TX_MOD_SYM.assign(MOD_SYM_LEN, CComplex());
 	RX_MOD_SYM.assign(MOD_SYM_LEN, CComplex());
+	GAIN.assign(fade_model ? MOD_SYM_LEN : 0, CComplex());
 	TX_MOD_IDX.assign(MOD_SYM_LEN, 0);
 	RX_LLR_BIT.assign(CODE_BIT_LEN, 0.0);
 	RX_LLR_SYM.assign((size_t)CODE_SYM_LEN * (GFq - 1), 0.0);
@@ -109,7 +127,7 @@ int CComm::FrontEnd()
 	Encode();
 	Puncture();
 	Modulate();
-	Channel_AWGN();
+	Channel();
 	return Demodulate();
 }
 
@@ -119,7 +137,7 @@ int CComm::FrontEndToChannel()
 	Encode();
 	Puncture();
 	Modulate();
-	return Channel_AWGN();
+	return Channel();
 }
 
 int CComm::FrontEndToModulate(unsigned int state_out[3])
@@ -151,7 +169,7 @@ int CComm::FrontEndToModulate(unsigned int state_out[3])
 	state_out[0] = (unsigned int)(Rand.IX % 61967ul);
 	state_out[1] = (unsigned int)(Rand.IY % 63443ul);
 	state_out[2] = (unsigned int)(Rand.IZ % 63599ul);
-	Rand.Skip(4ul * (unsigned long)MOD_SYM_LEN);
+	Rand.Skip(ChannelDraws());
 	return 0;
 }
 
@@ -346,9 +364,43 @@ int CComm::Channel_AWGN() // Comm.cpp:328-337: real AND imaginary noise are draw
 	return 0;
 }
 
+int CComm::Channel_Rayleigh() // include/nbldpc.h, "Rayleigh block fading on the device", steps 1-4
+{
+	const int nblk = (MOD_SYM_LEN + fade_block - 1) / fade_block;
+	const double S = sqrt(0.5);
+	std::vector<CComplex> h(nblk);
+	for (int k = 0; k < nblk; k++) {
+		h[k].Real = Rand.Rand_Norm(0, S);
+		h[k].Image = Rand.Rand_Norm(0, S);
+	}
+	for (int s = 0; s < MOD_SYM_LEN; s++) {
+		const CComplex &g = h[s / fade_block], &c = TX_MOD_SYM[s];
+		const double nr = Rand.Rand_Norm(0, sigma_n);
+		const double ni = Rand.Rand_Norm(0, sigma_n);
+		RX_MOD_SYM[s].Real = (g.Real * c.Real - g.Image * c.Image) + nr;
+		RX_MOD_SYM[s].Image = (g.Real * c.Image + g.Image * c.Real) + ni;
+		GAIN[s] = g;
+	}
+	return 0;
+}
+
 int CComm::Demodulate() // Comm.cpp:340-407
 {
 	const int w = GFq - 1;
+	if (fade_model) { // the lane's gains enter: the three paths of include/nbldpc.h, "demodulators with gains"
+		std::vector<int> src;
+		DemodSource(src);
+		std::vector<double> cons, rx, gain;
+		for (const CComplex &c : CONSTELLATION) { cons.push_back(c.Real); cons.push_back(c.Image); }
+		for (const CComplex &r : RX_MOD_SYM) { rx.push_back(r.Real); rx.push_back(r.Image); }
+		for (const CComplex &g : GAIN) { gain.push_back(g.Real); gain.push_back(g.Image); }
+		if (GeneralDemod())
+			DemodulateGeneral(CODE_SYM_LEN, Bit_Len_PerSYM, modOrder, MOD_SYM_LEN, cons.data(), src.data(), rx.data(), gain.data(), sigma_n, demod_metric,
+			                  nullptr, RX_LLR_SYM.data());
+		else if (modOrder == 2) DemodulateBpskCsi(CODE_SYM_LEN, Bit_Len_PerSYM, src.data(), rx.data(), gain.data(), sigma_n, RX_LLR_SYM.data());
+		else DemodulateQaryCsi(CODE_SYM_LEN, GFq, cons.data(), src.data(), rx.data(), gain.data(), sigma_n, RX_LLR_SYM.data());
+		return 0;
+	}
 	if (GeneralDemod()) {
 		std::vector<int> src;
 		DemodSource(src);
@@ -505,6 +557,112 @@ void CComm::DemodulateGeneral(int N, int p, int M, int L, const double *cons, co
 				}
 			}
 			for (int a = 1; a < q; a++) Ln[a - 1] = Ln[a - 1] + (D[0] - D[a]) / (2 * sigma * sigma);
+		}
+	}
+}
+
+// include/nbldpc.h, "demodulators with gains", general path: the function above with the distance to the faded point of sample s
+void CComm::DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, const double *gain, double sigma,
+                              int metric, const double *prior, double *out)
+{
+	if (!gain) { DemodulateGeneral(N, p, M, L, cons, src, rx, sigma, metric, prior, out); return; }
+	const int q = 1 << p;
+	int m = 0;
+	while ((1 << m) < M) m++;
+	std::vector<int> claim((size_t)L * m, -1);
+	for (int g = 0; g < N * p; g++)
+		if (src[g] >= 0) claim[src[g]] = g;
+	std::vector<double> d(M), D(q);
+	for (int n = 0; n < N; n++) {
+		double *Ln = out + (size_t)n * (q - 1);
+		for (int a = 1; a < q; a++) Ln[a - 1] = 0.0;
+		std::vector<int> pts;
+		for (int j = 0; j < p; j++) {
+			const int t = src[n * p + j];
+			if (t >= 0) pts.push_back(t / m);
+		}
+		std::sort(pts.begin(), pts.end());
+		pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+		for (int s : pts) {
+			int owner[8], nown = 0;
+			for (int i = 0; i < m; i++) owner[i] = -1;
+			for (int j = 0; j < p; j++) {
+				const int t = src[n * p + j];
+				if (t >= 0 && t / m == s) { owner[t % m] = j; nown++; }
+			}
+			const double re = rx[2 * s], im = rx[2 * s + 1], hr = gain[2 * s], hi = gain[2 * s + 1];
+			for (int c = 0; c < M; c++) {
+				const double cr = cons[2 * c], ci = cons[2 * c + 1];
+				const double pr = hr * cr - hi * ci;
+				const double pi = hr * ci + hi * cr;
+				d[c] = (re - pr) * (re - pr) + (im - pi) * (im - pi);
+				if (prior) {
+					double A = 0.0;
+					for (int i = 0; i < m; i++)
+						if (owner[i] < 0 && claim[(size_t)s * m + i] >= 0 && ((c >> (m - 1 - i)) & 1)) A = A + prior[claim[(size_t)s * m + i]];
+					d[c] = d[c] - (2 * sigma * sigma) * A;
+				}
+			}
+			for (int a = 0; a < q; a++) {
+				auto compatible = [&](int c) {
+					for (int i = 0; i < m; i++)
+						if (owner[i] >= 0 && ((c >> (m - 1 - i)) & 1) != ((a >> owner[i]) & 1)) return false;
+					return true;
+				};
+				bool first = true;
+				double dmin = 0.0;
+				for (int c = 0; c < M; c++)
+					if (compatible(c) && (first || d[c] < dmin)) { dmin = d[c]; first = false; }
+				if (metric == NBL_DEMOD_MAXLOG || nown == m) D[a] = dmin;
+				else {
+					double sum = 0.0;
+					for (int c = 0; c < M; c++)
+						if (compatible(c)) sum = sum + exp(-(d[c] - dmin) / (2 * sigma * sigma));
+					D[a] = dmin - (2 * sigma * sigma) * log(sum);
+				}
+			}
+			for (int a = 1; a < q; a++) Ln[a - 1] = Ln[a - 1] + (D[0] - D[a]) / (2 * sigma * sigma);
+		}
+	}
+}
+
+// BPSK with gains: z = hr re + hi im in place of re (Comm.cpp:356), then the bit -> symbol sums of Comm.cpp:364-378
+void CComm::DemodulateBpskCsi(int N, int p, const int *src, const double *rx, const double *gain, double sigma, double *out)
+{
+	const int w = (1 << p) - 1;
+	std::vector<double> bit((size_t)N * p);
+	for (int b = 0; b < N * p; b++) {
+		const int s = src[b];
+		if (s < 0) { bit[b] = 0; continue; }
+		const double z = gain[2 * s] * rx[2 * s] + gain[2 * s + 1] * rx[2 * s + 1];
+		bit[b] = -2 * z / (sigma * sigma);
+	}
+	for (int n = 0; n < N; n++)
+		for (int a = 1; a <= w; a++) {
+			double acc = 0;
+			for (int k = 0; k < p; k++)
+				if ((a & (1 << k)) != 0) acc += bit[(size_t)n * p + k];
+			out[(size_t)n * w + a - 1] = acc;
+		}
+}
+
+// one point per symbol with gains: the expression of Comm.cpp:394-395 on the faded points of the symbol's sample
+void CComm::DemodulateQaryCsi(int N, int q, const double *cons, const int *src, const double *rx, const double *gain, double sigma, double *out)
+{
+	const int w = q - 1;
+	for (int n = 0; n < N; n++) {
+		const int s = src[n];
+		if (s < 0) {
+			for (int a = 1; a < q; a++) out[(size_t)n * w + a - 1] = 0;
+			continue;
+		}
+		const double re = rx[2 * s], im = rx[2 * s + 1], hr = gain[2 * s], hi = gain[2 * s + 1];
+		const double p0r = hr * cons[0] - hi * cons[1];
+		const double p0i = hr * cons[1] + hi * cons[0];
+		for (int a = 1; a < q; a++) {
+			const double par = hr * cons[2 * a] - hi * cons[2 * a + 1];
+			const double pai = hr * cons[2 * a + 1] + hi * cons[2 * a];
+			out[(size_t)n * w + a - 1] = ((2 * re - p0r - par) * (par - p0r) + (2 * im - p0i - pai) * (pai - p0i)) / (2 * sigma * sigma);
 		}
 	}
 }

@@ -1,6 +1,8 @@
 // nbldpc_amd/host/comm.h -- CComm: one lane of the reference's link chain (Comm.h / Comm.cpp), minus the decoder it used to
 // own: all lanes share one CNBLDPC (code parameters + encoder) and their frames are decoded together by the caller.
 //   FrontEnd()    = GenerateMessage, Encode, Puncture, Modulate, Channel_AWGN, Demodulate      (Comm.cpp:181-189)
+//                   (NBL_CHANNEL=rayleigh: Channel_Rayleigh in place of Channel_AWGN, and the demodulators take the lane's gains;
+//                   include/nbldpc.h, "flat fading")
 //   TakeDecoded() = the symbol/bit unpacking of CComm::Decode after NBLDPC.Decoding             (Comm.cpp:421-443)
 //   Err()         = error counting                                                              (Comm.cpp:446-503)
 #pragma once
@@ -23,6 +25,8 @@ public:
 	int MSG_SYM_LEN = 0, MSG_BIT_LEN = 0, CODE_SYM_LEN = 0, CODE_BIT_LEN = 0, PUN_SYM_LEN = 0, PUN_BIT_LEN = 0;
 	int modOrder = 0, MOD_BIT_PER_SYM = 0, MOD_SYM_LEN = 0, MOD_BIT_LEN = 0;
 	double CodeRate = 0, sigma_n = 0;
+	int fade_model = 0, fade_block = 1; // NBL_FADING_* and the coherence in samples: NBL_CHANNEL=awgn|rayleigh (default awgn), NBL_FADE_BLOCK=k (default 1)
+	std::vector<CComplex> GAIN;        // [MOD_SYM_LEN] the gain of every received sample of this frame (Channel_Rayleigh)
 	int demod_metric = 0;              // NBL_DEMOD_* of the general demodulator (modOrder other than 2 and GFq): NBL_DEMOD_METRIC=maxlog|logsum
 	std::vector<int> TX_MSG_BIT_beforeCRC, TX_MSG_BIT, TX_MSG_SYM, TX_CODE_SYM, TX_CODE_BIT, PUN_SYM, PUN_BIT, TX_MOD_BIT;
 	std::vector<int> RX_DECODE_SYM, RX_DECODE_BIT, RX_MSG_SYM, RX_MSG_BIT;
@@ -37,7 +41,8 @@ public:
 	int FrontEnd();
 	int FrontEndToChannel(); // everything up to Channel_AWGN: the demodulator runs on the device
 	// everything up to Modulate: channel and demodulator run on the device.  The lane's generator state in front of the frame is
-	// returned and the generator is moved past the 4 * MOD_SYM_LEN uniform draws Channel_AWGN would have made (Comm.cpp:328-337).
+	// returned and the generator is moved past the uniform draws the channel would have made: ChannelDraws(), 4 * MOD_SYM_LEN for
+	// Channel_AWGN (Comm.cpp:328-337).
 	int FrontEndToModulate(unsigned int state_out[3]);
 	// which received sample carries each code bit (BPSK) / code symbol (q-ary); any other order: which label bit t = s m + i carries
 	// each code bit (kept bit k goes to t = k, -1 once k >= MOD_SYM_LEN m: the tail that MOD_SYM_LEN's floor drops)
@@ -50,6 +55,13 @@ public:
 	// the prior-aware form (include/nbldpc.h, nbl_decode_batch_samples_prior): prior [N p] per code bit; NULL IS the function above
 	static void DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, double sigma, int metric,
 	                              const double *prior, double *out);
+	// the gain-aware form (include/nbldpc.h, "demodulators with gains"): gain [L][2] per received sample, distances to the faded
+	// points; prior as above (may be NULL); gain == NULL IS the function above
+	static void DemodulateGeneral(int N, int p, int M, int L, const double *cons, const int *src, const double *rx, const double *gain, double sigma,
+	                              int metric, const double *prior, double *out);
+	// the BPSK and the one-point-per-symbol expressions with gains: src [N p] / [N] as DemodSource gives them, out [N][2^p - 1]
+	static void DemodulateBpskCsi(int N, int p, const int *src, const double *rx, const double *gain, double sigma, double *out);
+	static void DemodulateQaryCsi(int N, int q, const double *cons, const int *src, const double *rx, const double *gain, double sigma, double *out);
 	int GenerateMessage();
 	int GenPN();
 	void CRCEncode(int *seqOut, const int *seqIn, int seqInLen, int crcLen, int crc24Type);
@@ -58,6 +70,14 @@ public:
 	int Puncture();
 	int Modulate();
 	int Channel_AWGN();
+	// Rayleigh block fading (include/nbldpc.h, nbl_set_fading): nblk = ceil(L / fade_block) gains first, two Rand_Norm(0, sqrt(0.5))
+	// each, then the noise as Channel_AWGN draws it; RX = h * TX + n, the per-sample gains kept in GAIN
+	int Channel_Rayleigh();
+	int Channel() { return fade_model ? Channel_Rayleigh() : Channel_AWGN(); }
+	unsigned long ChannelDraws() const // uniform draws one frame's channel makes: nbl_channel_draws
+	{
+		return 4ul * (unsigned long)MOD_SYM_LEN + (fade_model ? 4ul * (unsigned long)((MOD_SYM_LEN + fade_block - 1) / fade_block) : 0ul);
+	}
 	int Demodulate();
 	int TakeDecoded(const int *decoded_sym, bool converged);
 	int Err(CSimulation &sim);

@@ -55,6 +55,11 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 		for (auto &x : extra)
 			if (x->SetDemodulator(lanes[0]->modOrder, lanes[0]->MOD_SYM_LEN, cons.data(), src.data(), lanes[0]->demod_metric) != 0) { error = x->LastError(); return false; }
 	}
+	if (device_noise && lanes[0]->fade_model) { // the device-side channel fades as the lanes would (NBL_CHANNEL / NBL_FADE_BLOCK)
+		if (code.SetFading(lanes[0]->fade_model, lanes[0]->fade_block) != 0) { error = code.LastError(); return false; }
+		for (auto &x : extra)
+			if (x->SetFading(lanes[0]->fade_model, lanes[0]->fade_block) != 0) { error = x->LastError(); return false; }
+	}
 	if (!device_demod && code.IddPasses() > 1) {
 		error = "NBL_IDD_PASSES=" + std::to_string(code.IddPasses()) + ": iterative demapping runs behind the device-side demodulator; NBL_DEVICE_DEMOD=0 switches that off";
 		std::cerr << error << std::endl;
@@ -69,12 +74,12 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 		for (auto &x : extra)
 			if (x->SetTransmitter(g, sim.crcLen, sim.randomMsg, sim.parallel, l0.modOrder, l0.MOD_SYM_LEN) != 0) { error = x->LastError(); return false; }
 		// one frame moves a lane's PN register (K p - crcLen) * parallel clocks (none with an all-zero message) and its generator
-		// 4 L draws: both are fixed maps, tabulated once with the library's helpers
+		// nbl_channel_draws draws (4 L, plus 4 per fading block): both are fixed maps, tabulated once with the library's helpers
 		const uint64_t clocks = sim.randomMsg ? (uint64_t)(l0.MSG_BIT_LEN - l0.crcLen) * (uint64_t)sim.parallel : 0;
 		pn_frame.resize(2048);
 		for (int s = 0; s < 2048; s++) { pn_frame[s] = (uint16_t)s; nbl_pn_advance(&pn_frame[s], clocks); }
 		uint32_t one[3] = {1, 1, 1};
-		nbl_rand_advance(one, 4ull * (uint64_t)l0.MOD_SYM_LEN);
+		nbl_rand_advance(one, code.ChannelDraws());
 		for (int k = 0; k < 3; k++) rs_frame[k] = one[k];
 		pn_cur.assign(sim.parallel, 0);
 		rs_cur.assign((size_t)3 * sim.parallel, 0);
@@ -82,6 +87,7 @@ bool CLink::Initial(const std::string &profile, const std::vector<int> &device_l
 	for (int slot = 0; slot < (pipeline ? 2 : 1); slot++) {
 		if (device_tx) pn_batch[slot].assign(sim.parallel, 0);
 		rx_batch[slot].assign(device_demod && !device_noise ? (size_t)2 * lanes[0]->MOD_SYM_LEN * sim.parallel : 0, 0.0);
+		gain_batch[slot].assign(device_demod && !device_noise && lanes[0]->fade_model ? (size_t)2 * lanes[0]->MOD_SYM_LEN * sim.parallel : 0, 0.0);
 		txi_batch[slot].assign(device_noise && !device_tx ? (size_t)lanes[0]->MOD_SYM_LEN * sim.parallel : 0, 0);
 		state_batch[slot].assign(device_noise ? (size_t)3 * sim.parallel : 0, 0);
 		L_batch[slot].assign(device_demod ? 0 : per * sim.parallel, 0.0);
@@ -149,6 +155,13 @@ void CLink::FrontEnds(int slot)
 				for (int s = 0; s < L; s++) {
 					rx[2 * s] = lanes[i]->RX_MOD_SYM[s].Real;
 					rx[2 * s + 1] = lanes[i]->RX_MOD_SYM[s].Image;
+				}
+				if (lanes[i]->fade_model) {
+					double *gn = &gain_batch[slot][(size_t)i * L * 2];
+					for (int s = 0; s < L; s++) {
+						gn[2 * s] = lanes[i]->GAIN[s].Real;
+						gn[2 * s + 1] = lanes[i]->GAIN[s].Image;
+					}
 				}
 			} else {
 				lanes[i]->FrontEnd();
@@ -220,7 +233,8 @@ bool CLink::Decode(int slot)
 			rc[gidx] = dec.DecodingBatchResident(slot, sigma, hi - lo, device_tx ? nullptr : &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo]);
 		else if (hi > lo)
 			rc[gidx] = device_demod
-			    ? dec.DecodingBatchSamples(&rx_batch[slot][rxper * lo], sigma, hi - lo, &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo])
+			    ? dec.DecodingBatchSamples(&rx_batch[slot][rxper * lo], sigma, hi - lo, &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo],
+			                               gain_batch[slot].empty() ? nullptr : &gain_batch[slot][rxper * lo])
 			    : dec.DecodingBatch(&L_batch[slot][per * lo], hi - lo, &out_batch[(size_t)code.CodeLen * lo], &conv[lo], &iters[lo]);
 	};
 	if (G == 1) shard(0);

@@ -16,6 +16,7 @@ public:
 	bool device_demod = true;          // ship received samples, demodulate on the GPU (bit-identical L_ch);
 	                                   // NBL_DEVICE_DEMOD=0: build L_ch on the host as the reference's Demodulate does
 	std::vector<double> rx_batch[2];   // [parallel][MOD_SYM_LEN][2]
+	std::vector<double> gain_batch[2]; // [parallel][MOD_SYM_LEN][2] NBL_CHANNEL=rayleigh behind the host channel: the gains, uploaded beside the samples
 	bool device_noise = true;          // AWGN channel + CRand on the GPU as well (bit-identical samples);
 	                                   // NBL_DEVICE_NOISE=0 draws the noise on the host threads.  Needs device_demod.
 	std::vector<unsigned char> txi_batch[2]; // [parallel][MOD_SYM_LEN] constellation indices
@@ -26,7 +27,7 @@ public:
 	std::vector<uint16_t> pn_cur, pn_batch[2]; // [parallel] PN register of every lane: now / in front of the slot's frame
 	std::vector<unsigned int> rs_cur;  // [parallel][3] generator state of every lane now
 	std::vector<uint16_t> pn_frame;    // register state -> state one frame later
-	unsigned int rs_frame[3] = {1, 1, 1}; // multipliers of one frame's 4 L uniform draws
+	unsigned int rs_frame[3] = {1, 1, 1}; // multipliers of one frame's uniform draws (nbl_channel_draws: 4 L, plus 4 per fading block)
 	bool Transmit(int slot);           // device-side transmit chain + channel of the slot's frames
 	bool count_ok = true;
 	bool channel_ok[2] = {true, true};

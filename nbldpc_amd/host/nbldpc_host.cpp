@@ -271,12 +271,26 @@ int CNBLDPC::SetDemodulator(int mod_order, int n_mod_sym, const double *constell
 	return 0;
 }
 
-int CNBLDPC::DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters)
+int CNBLDPC::SetFading(int model, int coherence)
+{
+	if (!dec) { error = "decoder not initialised"; return -1; }
+	const nbl_fading_desc f = {model, coherence};
+	nbl_status st = nbl_set_fading(dec, &f);
+	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
+	return 0;
+}
+
+int CNBLDPC::DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters, const double *gain)
 {
 	if (!dec) { error = "decoder not initialised"; return -1; }
 	const nbl_idd_params idd = {idd_passes, idd_soft};
-	nbl_status st = idd_passes > 1 ? nbl_decode_batch_samples_idd(dec, rx, sigma, B, &idd, out, converged, iters, nullptr)
-	                               : nbl_decode_batch_samples(dec, rx, sigma, B, out, converged, iters);
+	nbl_status st;
+	if (gain)
+		st = idd_passes > 1 ? nbl_decode_batch_samples_idd_csi(dec, rx, gain, sigma, B, &idd, out, converged, iters, nullptr)
+		                    : nbl_decode_batch_samples_csi(dec, rx, gain, nullptr, sigma, B, out, converged, iters);
+	else
+		st = idd_passes > 1 ? nbl_decode_batch_samples_idd(dec, rx, sigma, B, &idd, out, converged, iters, nullptr)
+		                    : nbl_decode_batch_samples(dec, rx, sigma, B, out, converged, iters);
 	if (st != NBL_OK) { error = nbl_last_error(dec); std::cerr << error << std::endl; return (int)st; }
 	return 0;
 }

@@ -38,7 +38,11 @@ public:
 	int DecodingBatch(const double *L_ch, int B, int *out, uint8_t *converged, int *iters);
 	// device-side demodulation (replaces CComm::Demodulate, Comm.cpp:340-407): rx [B][L][2] received samples
 	int SetDemodulator(int mod_order, int n_mod_sym, const double *constellation, const int *src, int metric = 0); // metric: NBL_DEMOD_*, general orders only
-	int DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters);
+	// gain [B][L][2] (may be null): coherent reception over a flat-fading channel (nbl_decode_batch_samples_csi / _idd_csi)
+	int DecodingBatchSamples(const double *rx, double sigma, int B, int *out, uint8_t *converged, int *iters, const double *gain = nullptr);
+	// the device-side channel's fading model (nbl_set_fading): model NBL_FADING_*, coherence in samples
+	int SetFading(int model, int coherence);
+	uint64_t ChannelDraws() const { return dec ? nbl_channel_draws(dec) : 0; } // uniform draws a frame moves a lane's generator
 	// per-bit LLRs in place of symbol LLRs (the RX_LLR_BIT -> RX_LLR_SYM loop of Comm.cpp:359-373 runs on the device): bit_llr [B][CodeLen p],
 	// ln P(bit = 1) / P(bit = 0), bit j of a symbol has value 2^j, a punctured bit is 0.0.  No demodulator has to be set.
 	int DecodingBatchBits(const double *bit_llr, int B, int *out, uint8_t *converged, int *iters);

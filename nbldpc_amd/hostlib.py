@@ -27,6 +27,12 @@ def load():
         L.nblh_channel.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.nblh_demod_general.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
         L.nblh_demod_general_prior.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p]
+        L.nblh_channel_fading.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_ulonglong)]
+        L.nblh_demod_csi.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                     C.c_int, C.c_int, C.c_void_p]
+        L.nbl_rand_advance.argtypes = [C.c_void_p, C.c_uint64]  # (libnbldpc_hip.so's helper, pure host arithmetic)
+        L.nbl_rand_advance.restype = None
         L.nblh_simulate.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int]
         L.nblh_encode.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
         L.nblh_generator.argtypes = [C.c_char_p, C.c_void_p]
@@ -122,6 +128,57 @@ def demod_general_prior(N, p, points, src, rx, sigma, metric, prior):
     if rc != 0:
         raise RuntimeError(f"nblh_demod_general_prior rc={rc}")
     return out
+
+
+def channel_fading(workdir_path, ebn0, frames, L, P, coherence):
+    """Host link chain up to the Rayleigh block-fading channel (CComm::Channel_Rayleigh, `coherence` samples per gain):
+    (rx [B][L][2], gain [B][L][2], tx_index [B][L] uint8, state [B][3] uint32, sigma, draws), B = frames * P; draws = the uniform draws one
+    frame moves a lane's generator.  No GPU."""
+    B = frames * P
+    rx = np.zeros((B, L, 2))
+    gain = np.zeros((B, L, 2))
+    txi = np.zeros((B, L), dtype=np.uint8)
+    state = np.zeros((B, 3), dtype=np.uint32)
+    sig = C.c_double(0)
+    draws = C.c_ulonglong(0)
+    with workdir(workdir_path):
+        rc = load().nblh_channel_fading(b"NBLDPC.Profile.txt", ebn0, frames, int(coherence), rx.ctypes.data, gain.ctypes.data, txi.ctypes.data,
+                                        state.ctypes.data, C.byref(sig), C.byref(draws))
+    if rc != L:
+        raise RuntimeError(f"nblh_channel_fading rc={rc} (expected MOD_SYM_LEN {L})")
+    return rx, gain, txi, state, sig.value, int(draws.value)
+
+
+def demod_csi(path, N, p, points, src, rx, gain, sigma, metric=0, prior=None):
+    """The host layer's demodulators with per-sample gains (include/nbldpc.h, "demodulators with gains") on rx, gain [B][L][2] ->
+    [B][N][2^p - 1].  path "general": CComm::DemodulateGeneral's gain overload (src [N p] label-bit indices, metric, prior [B][N p] or
+    None; gain None = the gain-less function); "bpsk": src [N p] sample indices; "qary": src [N] sample indices.  No GPU."""
+    code = {"general": 0, "bpsk": 1, "qary": 2}[path]
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    src = np.ascontiguousarray(src, dtype=np.int32)
+    rx = np.ascontiguousarray(rx, dtype=np.float64)
+    B, L = rx.shape[0], rx.shape[1]
+    assert rx.shape == (B, L, 2) and points.shape[1] == 2 and src.shape == ((N,) if code == 2 else (N * p,))
+    if gain is not None:
+        gain = np.ascontiguousarray(gain, dtype=np.float64)
+        assert gain.shape == rx.shape, gain.shape
+    if prior is not None:
+        prior = np.ascontiguousarray(prior, dtype=np.float64)
+        assert prior.shape == (B, N * p), prior.shape
+    out = np.zeros((B, N, (1 << p) - 1))
+    rc = load().nblh_demod_csi(code, N, p, points.shape[0], L, points.ctypes.data, src.ctypes.data, rx.ctypes.data,
+                               None if gain is None else gain.ctypes.data, None if prior is None else prior.ctypes.data, float(sigma), int(metric), B,
+                               out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"nblh_demod_csi rc={rc}")
+    return out
+
+
+def rand_advance(state, draws):
+    """nbl_rand_advance of the C ABI (pure host arithmetic): the generator state [3] after `draws` uniform draws"""
+    s = np.array(state, dtype=np.uint32)
+    load().nbl_rand_advance(s.ctypes.data, int(draws))
+    return s
 
 
 def simulate(workdir_path, device=0, max_rows=32):
