@@ -247,6 +247,49 @@ nbl_status nbl_create_layered_ex(const nbl_code_desc *code, const uint16_t *gf_m
 nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                                  const nbl_params *params, const int32_t *layer_of, int device, nbl_decoder **out);
 
+/* ---- FHT sum-product decoding: the fast check node of non-binary BP, flooding and layered ----------------------------------------
+ * Over GF(2^p) the box-plus of the sum-product rule is an XOR convolution of probability vectors, and the Walsh-Hadamard transform
+ * (WHT) turns it into a pointwise product: a check costs 2 dc transforms of q log2 q butterflies instead of 3 (dc - 2) sums of q^2
+ * terms.  The transform subtracts, so outputs far below a vector's largest are rounding noise and are floored.  This is therefore NOT
+ * another evaluation of method 1's check node: it is a decoder kind of its own, with its own definition and its own parity statement
+ * (tests/fht_ref.py restates it in numpy).
+ *   The FHT check-node update of inputs in_0 .. in_{dc-1} (q-vectors of LLRs, slot 0 = 0) with edge coefficients h_d.  All arithmetic is
+ *   IEEE double, every product and every sum rounded on its own, no contraction:
+ *   1. Check domain: p_d[h_d a] = in_d[a] (as the log-QSPA check node does, NBLDPC.cpp:1623-1632).
+ *   2. m_d = max_y p_d[y];  u_d[y] = exp(p_d[y] - m_d).
+ *   3. U_d = WHT(u_d), in place: stages with stride s = 1, 2, 4, .., q/2 in that order; in a stage, for every i with bit s clear,
+ *      (x[i], x[i+s]) <- (x[i] + x[i+s], x[i] - x[i+s]).  The order inside a stage is immaterial.
+ *   4. Fwd_1 = U_0, Fwd_{k+1} = Fwd_k * U_k;  Bwd_{dc-2} = U_{dc-1}, Bwd_{k-1} = Bwd_k * U_k (elementwise);
+ *      V_0 = Bwd_0, V_{dc-1} = Fwd_{dc-1}, otherwise V_d = Fwd_d * Bwd_d.  (dc = 2: V_0 = U_1, V_1 = U_0.)
+ *   5. v_d = WHT(V_d), the same stages, left unnormalised (the factor 1/q cancels in step 7).
+ *   6. t = max_y v_d[y] (> 0: sum_y v_d[y] = q * prod_k U_k[0] > 0);  v'_d[y] = max(v_d[y], t * 2^-NBL_FHT_FLOOR_LOG2).  The floor is part
+ *      of the method, not a tuning knob: no c2v entry lies more than 40 ln 2 = 27.7 nats below its vector's largest; an entry at the
+ *      floor carries a relative error of about 2^-10, anything above it proportionally less.
+ *   7. c_d[y] = log(v'_d[y]) - log(v'_d[0]), c_d[0] = 0;  c2v_d[a] = c_d[h_d a].
+ *   Consequences: given equal u the v are bit-identical between implementations (steps 3-5 are adds, subtracts and products in a fixed
+ *   order); only exp and log differ.  Inputs are assumed finite.  A vector wider than about 745 nats becomes one-hot and its partners'
+ *   outputs saturate at the floor: unlike log-QSPA the method has a bounded range by construction.
+ *   Schedules.  Flooding (flags 0): the reference's log-QSPA iteration (NBLDPC.cpp:643-775) -- decision, syndrome, variable-node pass
+ *   with the 0.5 / 0.5 per-edge damping -- with the check-node update above in place of :747-767.  Layered (NBL_FHT_LAYERED): word for
+ *   word the schedule of nbl_create_layered_bp above with the same replacement: the same layer rules, the same nbl_layer_greedy, the
+ *   same v2c state and damping.
+ *   Parity.  For a vector x let w(x) = exp(x - max x), the implicit 0 of slot 0 included.  Hard decisions, converged flags and
+ *   iteration counts equal those of the FP64 numpy restatement on inputs whose decisions have a margin; for post, c2v and v2c,
+ *   |w(x_gpu) - w(x_ref)| stays within 16 times the deviation between the restatement in FP64 and in 80-bit arithmetic
+ *   (tests/fht_ref.py records it per case).  A statement in the probability domain: LLRs of entries near the floor are not pinned.
+ * nbl_create_fht: NBL_METHOD_BP only (no OSD, no extension parameters).  flags 0 = flooding (a non-NULL layer_of is NBL_ERR_ARG);
+ * NBL_FHT_LAYERED = layered, layer_of == NULL selects the greedy assignment; an unknown flag bit is NBL_ERR_ARG.  Any other method is
+ * NBL_ERR_UNSUPPORTED (the message names method 1); every assignment error of nbl_create_layered keeps its status and text; everything
+ * nbl_create refuses is refused the same way; all of it before the device is touched.  No shape is refused for its LDS (maxdc q 8
+ * bytes, at most 16 KB).  Every decode entry point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and
+ * extrinsic), fixed_iters, poll_every and the active list, the transmitter, channel and error count work unchanged on such a decoder.
+ * nbl_read_state returns post, c2v and v2c as on the corresponding log-QSPA decoder; nbl_get_layers works on the layered kind and is
+ * NBL_ERR_ARG on the flooding kind.  Method 1 through nbl_create stays the exact log-QSPA. */
+#define NBL_FHT_FLOOR_LOG2 40
+#define NBL_FHT_LAYERED 1u
+nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                          const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the
  * reference's return value).  iters: [B] iteration of the first zero syndrome, or max_iter.

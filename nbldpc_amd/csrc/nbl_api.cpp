@@ -48,6 +48,7 @@ struct nbl_decoder {
 	// place; EMS keeps no v2c, T-EMS (NBL_LAYERED_DAMPED) and log-QSPA keep the per-edge v2c their damping reads, updated in place by the
 	// edge's check
 	bool layered = false;
+	bool fht = false;         // nbl_create_fht: the FHT sum-product check node in place of the exact one (flooding or layered)
 	int n_layers = 0;
 	std::vector<int> h_layer_of; // [M] the assignment in use
 	std::vector<int> h_lay_off;  // [n_layers + 1] offsets into ly.chk
@@ -222,7 +223,7 @@ static bool small_enabled()
 // The kernel choice of this decoder as it stands (nbl_plan.cpp): once per workspace check and once per decode, never per launch
 static NblPlan plan_of(const nbl_decoder *d)
 {
-	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled());
+	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled(), d->fht);
 }
 
 static nbl_status ensure_workspace(nbl_decoder *d, int B)
@@ -501,7 +502,8 @@ extern "C" int32_t nbl_layer_greedy(const nbl_code_desc *code, int32_t *layer_of
 struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
-                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out);
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out,
+                              bool fht = false);
 
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
@@ -530,6 +532,22 @@ extern "C" nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uin
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
 }
 
+// FHT sum-product decoding (include/nbldpc.h): flooding without a LayerReq, layered with the request of nbl_create_layered_bp -- the same
+// assignment rules, the same v2c state
+extern "C" nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                     const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	if (!out) return NBL_ERR_ARG;
+	*out = nullptr;
+	if (flags & ~(uint32_t)NBL_FHT_LAYERED)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_FHT_LAYERED = 1 is the only one defined)");
+	if (!(flags & NBL_FHT_LAYERED) && layer_of)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or set "
+		                                         "NBL_FHT_LAYERED)");
+	const LayerReq lay = {layer_of, 0, true};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_FHT_LAYERED) ? &lay : nullptr, device, out, true);
+}
+
 extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
 {
 	if (!d || !d->layered) return NBL_ERR_ARG;
@@ -539,7 +557,7 @@ extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, in
 }
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
-                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out)
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht)
 {
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
@@ -553,6 +571,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	std::string field_err;
 	const int poly = validate_field(q, gf_mul, gf_inv, field_err);
 	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
+	if (fht && params->method != NBL_METHOD_BP)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_fht runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, "
+		                                                 "which no other method's check node is");
 	if (lay && lay->bp && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_layered_bp runs log-QSPA (method 1) only: the layered schedule of EMS (method 2) is behind "
 		                                                 "nbl_create_layered, that of T-EMS (method 4) behind nbl_create_layered_ex with NBL_LAYERED_DAMPED");
@@ -744,6 +765,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		d->h_layer_of = layer_of;
 		d->h_lay_off = lay_off;
 	}
+	d->fht = fht;
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;
@@ -906,6 +928,16 @@ extern "C" nbl_status nbl_debug_plan(const nbl_code_desc *code, const nbl_params
 	return NBL_OK;
 }
 
+// The same for a decoder nbl_create_fht would make; fht_flags: NBL_FHT_* of include/nbldpc.h
+extern "C" nbl_status nbl_debug_plan_fht(const nbl_code_desc *code, const nbl_params *params, uint32_t fht_flags, int32_t force_generic, int32_t record_state,
+                                         nbl_plan_info *out)
+{
+	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
+	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (fht_flags & NBL_FHT_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), true);
+	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
+	return NBL_OK;
+}
+
 // The one launch of check-node kernel `cn`; fused: with the variable-node pass inside (w then carries c2v_prev).  The layered kernels
 // run once per layer and are launched where the layers are walked (enqueue_window).
 static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
@@ -924,6 +956,7 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_BP64: HIP_TRY(d, nbl_launch_cn_bp64(g, w, r, fused, st)); break;
 	case NBL_CN_BP_SMALL: HIP_TRY(d, nbl_launch_cn_bp_small(g, w, r, fused, st)); break;
 	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
+	case NBL_CN_FHT: HIP_TRY(d, nbl_launch_cn_fht(g, w, r, st)); break;
 	case NBL_CN_BSTEMS: HIP_TRY(d, nbl_launch_cn_bstems(g, w, r, st)); break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
@@ -977,6 +1010,7 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 				case NBL_CN_EMS_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_TEMS_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_BP_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				case NBL_CN_FHT_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				default: d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED;
 				}
 			}

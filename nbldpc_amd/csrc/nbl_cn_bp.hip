@@ -4,22 +4,7 @@
 #include "nbl_device.h"
 #include "nbl_kernels.h"
 #include "nbl_cn_bp_core.h"
-
-// entry lane + 64 i of edge d's v2c vector
-template <int Q> struct BpV2cInput {
-	const double *V; // the codeword's v2c block
-	const int *epos; // the check's row of c_epos
-	int lane;
-	__device__ __forceinline__ void operator()(int d, double (&v)[Fld<Q>::NS]) const
-	{
-		const double *Vd = V + (size_t)epos[d] * Q;
-#pragma unroll
-		for (int i = 0; i < Fld<Q>::NS; i++) {
-			int a = lane + 64 * i;
-			v[i] = (a < Q) ? Vd[a] : 0.0;
-		}
-	}
-};
+#include "nbl_cn_bp_inputs.h"
 
 template <int Q>
 __global__ __launch_bounds__(64) void cn_bp_kernel(NblGraphDev g, NblWork w, NblRun r)

@@ -18,12 +18,12 @@
 #include "nbl_device.h"
 #include "nbl_kernels.h"
 #include "nbl_cn_bp_core.h"
+#include "nbl_cn_bp_inputs.h"
 
 // the checks of one layer: one wave per (codeword, check); grid = count * (codeword slots)
 template <int Q>
 __global__ __launch_bounds__(64) void cn_bp_layered_kernel(NblGraphDev g, NblWork w, NblRun r, NblLayerDev ly, int offset, int count)
 {
-	constexpr int NS = Fld<Q>::NS;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	const int lane = lane_id();
 	const int b = nbl_codeword(w, r, blockIdx.x / count), m = ly.chk[offset + blockIdx.x % count];
@@ -33,47 +33,8 @@ __global__ __launch_bounds__(64) void cn_bp_layered_kernel(NblGraphDev g, NblWor
 	const double *L = w.Lch + (size_t)b * g.N * Q;
 	double *Cb = w.c2v + (size_t)b * g.E * Q;
 	double *Vb = w.v2c + (size_t)b * g.E * Q;
-	// input of edge j, variable n: P = L_ch[n], then + c2v of each of n's edges in n's order (the CURRENT values); raw = P - c2v of this
-	// edge; damped against the stored v2c of this edge where the two decide differently; stored back (include/nbldpc.h)
-	auto input = [&](int j, double (&v)[NS]) {
-		const int *row = ly.nbr + (size_t)(c0 + j) * NBL_LAYER_ROW;
-		const int dv = row[1];
-		const double *Ln = L + (size_t)row[0] * Q;
-		const double *own = Cb + (size_t)(c0 + j) * Q;
-		double *Vd = Vb + (size_t)g.c_epos[c0 + j] * Q;
-		double ov[NS];
-#pragma unroll
-		for (int i = 0; i < NS; i++) {
-			int a = lane + 64 * i;
-			v[i] = (a < Q) ? Ln[a] : 0.0;
-			ov[i] = (a < Q) ? Vd[a] : 0.0;
-		}
-		for (int d = 0; d < dv; d++) {
-			const double *Cd = Cb + (size_t)row[4 + d] * Q;
-#pragma unroll
-			for (int i = 0; i < NS; i++) {
-				int a = lane + 64 * i;
-				if (a < Q) v[i] = v[i] + Cd[a];
-			}
-		}
-#pragma unroll
-		for (int i = 0; i < NS; i++) {
-			int a = lane + 64 * i;
-			if (a < Q) v[i] = v[i] - own[a];
-		}
-		const int before = wave_decide<NS>(ov, lane, Q);
-		const int after = wave_decide<NS>(v, lane, Q);
-		if (before != after) {
-#pragma unroll
-			for (int i = 0; i < NS; i++) v[i] = __dadd_rn(__dmul_rn(r.damp_old, ov[i]), __dmul_rn(r.damp_new, v[i]));
-		}
-#pragma unroll
-		for (int i = 0; i < NS; i++) {
-			int a = lane + 64 * i;
-			if (a == 0) v[i] = 0.0;
-			if (a < Q) Vd[a] = v[i];
-		}
-	};
+	// (the input former of the damped layered schedule: nbl_cn_bp_inputs.h, shared with nbl_cn_fht_layered.hip)
+	const BpLayeredInput<Q> input = {L, Cb, Vb, ly.nbr, g.c_epos, c0, lane, r.damp_old, r.damp_new};
 	bp_check_node<Q>(g, smem, c0, dc, Cb + (size_t)c0 * Q, input);
 }
 

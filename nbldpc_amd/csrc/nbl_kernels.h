@@ -37,6 +37,11 @@ hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, co
 // then the programme of nbl_cn_bp_core.h.  LDS: (3 maxdc + 5) q 8 bytes, at most 59,392 B for the shapes the ABI accepts
 hipError_t nbl_launch_cn_bp_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// FHT sum-product check node (nbl_create_fht; nbl_cn_fht.hip flooding, nbl_cn_fht_layered.hip the checks of one layer): the programme of
+// nbl_cn_fht_core.h on the inputs of nbl_cn_bp_inputs.h.  LDS: maxdc q 8 bytes, at most 16 KB
+hipError_t nbl_launch_cn_fht(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_fht_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 size_t nbl_ems256_lds_bytes(int nm);
 hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);

@@ -32,14 +32,18 @@ NblShape nbl_shape(const nbl_code_desc *code)
 
 static const char *const cn_names[NBL_CN_COUNT] = {
 	"ems256", "ems_small", "ems64", "ems", "tems64", "tems256", "tems_small", "tems", "bp256", "bp64", "bp_small", "bp",
-	"bstems", "ems_layered", "tems_layered", "none", "bp_layered"};
+	"bstems", "ems_layered", "tems_layered", "none", "bp_layered", "fht", "fht_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &, bool layered, int force_generic, bool record_state,
-                 bool small_on)
+                 bool small_on, bool fht)
 {
 	NblPlan pl{NBL_CN_NONE, false, false, true};
+	if (fht) { // one general kernel per schedule: never fused, no debug switch moves it; both schedules read v2c (flooding: the inputs)
+		pl.cn = layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT;
+		return pl;
+	}
 	if (layered) { // one c2v buffer updated in place: never fused; T-EMS and log-QSPA keep the v2c their damping reads
 		pl.cn = prm.method == NBL_METHOD_TEMS ? NBL_CN_TEMS_LAYERED : prm.method == NBL_METHOD_BP ? NBL_CN_BP_LAYERED : NBL_CN_EMS_LAYERED;
 		pl.want_v2c = prm.method == NBL_METHOD_TEMS || prm.method == NBL_METHOD_BP;

@@ -10,6 +10,7 @@ enum NblCn {
 	NBL_CN_BSTEMS, NBL_CN_EMS_LAYERED, NBL_CN_TEMS_LAYERED,
 	NBL_CN_NONE, // method 6: no iteration
 	NBL_CN_BP_LAYERED,
+	NBL_CN_FHT, NBL_CN_FHT_LAYERED, // nbl_create_fht: the FHT sum-product check node, flooding and layered
 	NBL_CN_COUNT
 };
 
@@ -22,9 +23,10 @@ struct NblPlan {
 
 NblShape nbl_shape(const nbl_code_desc *code);
 // force_generic: nbl_debug_force_generic's value (1 = the general kernel, 2 = the specialised one, neither fused);
-// small_on: the kernels NBL_NO_SMALL switches off (EMS-small, T-EMS-small, BP-small, EMS-64) may be chosen
+// small_on: the kernels NBL_NO_SMALL switches off (EMS-small, T-EMS-small, BP-small, EMS-64) may be chosen;
+// fht: an nbl_create_fht decoder (method 1; `layered` says which of its two schedules)
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
-                 bool small_on);
+                 bool small_on, bool fht = false);
 const char *nbl_cn_name(NblCn cn);
 
 // What each specialised kernel can run, beside the kernel (its LDS arithmetic lives there); nbl_plan is the only caller.

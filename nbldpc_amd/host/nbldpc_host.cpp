@@ -115,7 +115,22 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = lay_bp    ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
+	// NBL_BP_CHECK=fht: the FHT sum-product check node in place of the exact one (nbl_create_fht; off by default, NBL_BP_CHECK=exact names
+	// the default).  A log-QSPA profile (method 1) without OSD only; combines with NBL_SCHEDULE=flooding (or unset) and layered-bp
+	const char *bpc = getenv("NBL_BP_CHECK");
+	const bool fht = bpc && std::string(bpc) == "fht";
+	if (bpc && !fht && std::string(bpc) != "exact") {
+		error = std::string("NBL_BP_CHECK=") + bpc + ": unknown check node (exact, fht)";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (fht && (sim.decodeMethod != BP_DECODE || osd || (layered && !lay_bp))) {
+		error = "NBL_BP_CHECK=fht: the FHT check node is defined for log-QSPA (method 1) without OSD only, under NBL_SCHEDULE=flooding or layered-bp";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	nbl_status st = fht       ? nbl_create_fht(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT_LAYERED : 0u, device, &dec)
+	                : lay_bp  ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
 	                : damped  ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
 	                : layered ? nbl_create_layered(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
 	                          : nbl_create_osd(&code, mul.data(), inv.data(), &p, sim.decodeMethod == BS_TEMS_DECODE ? &ext : nullptr,
