@@ -6,7 +6,7 @@
 // TRUE value lies farther than b ulp from the midpoint between two neighbouring doubles, every result within that bound --
 // glibc's included -- is the correctly rounded one.  These routines compute the value to ~2^-100 relative, return the
 // correctly rounded double, and tell the caller whether it is `certain` (away from a midpoint by more than the band); the
-// uncertain few per cent are evaluated by the host's own libm (nbl_api.cpp).  sqrt and the divisions of CRand are IEEE
+// uncertain few per cent are evaluated by the host's own libm (nbl_api_channel.cpp).  sqrt and the divisions of CRand are IEEE
 // operations and need no such care.
 //
 // Host and device compile the same code (the host build is how tests/test_ddmath.py compares it with glibc without a GPU).

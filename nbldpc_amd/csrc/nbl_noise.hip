@@ -8,7 +8,7 @@
 // starts from the lane's state times a tabulated power.  Divisions, products and sqrt are IEEE operations; log and cos are
 // evaluated in double-double (nbl_ddmath.h) and come with a verdict: `certain` results equal glibc's by glibc's own error
 // bound, the rest (about one value in six) is listed for the host, which evaluates exactly those with its libm
-// (nbl_decode_batch_noise in nbl_api.cpp) before the samples are formed.  Three kernels:
+// (run_channel in nbl_api_channel.cpp) before the samples are formed.  Three kernels:
 //   noise_gen_kernel     one thread per normal draw: u1, u2, log(1 - u1), cos(2 pi u2) -> fn[draw] = {lg, cs}; uncertain ones listed
 //   noise_patch_kernel   host-evaluated values written over the listed entries
 //   noise_finish_kernel  RX = TX + (0 + sigma * cs * sqrt(-2 lg)) in the reference's expression order
