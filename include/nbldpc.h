@@ -280,13 +280,17 @@ nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_m
  * nbl_create_fht: NBL_METHOD_BP only (no OSD, no extension parameters).  flags 0 = flooding (a non-NULL layer_of is NBL_ERR_ARG);
  * NBL_FHT_LAYERED = layered, layer_of == NULL selects the greedy assignment; an unknown flag bit is NBL_ERR_ARG.  Any other method is
  * NBL_ERR_UNSUPPORTED (the message names method 1); every assignment error of nbl_create_layered keeps its status and text; everything
- * nbl_create refuses is refused the same way; all of it before the device is touched.  No shape is refused for its LDS (maxdc q 8
- * bytes, at most 16 KB).  Every decode entry point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and
+ * nbl_create refuses is refused the same way, except the check-degree limit, which is 32 here (NBL_FHT_MAX_CHECK_DEGREE: check degrees
+ * 2 .. 32, variable degrees 1 .. 8; a larger check is NBL_ERR_ARG and the message names 32); all of it before the device is touched.  The
+ * update above is generic in dc: a code whose checks all have degree 8 or less runs it with the transformed inputs in registers, any other
+ * code in a layout whose storage does not grow with the degree; the two evaluate the same operations in the same order and give the same
+ * bits.  No shape is refused for its LDS (maxdc q 8 bytes, at most 64 KB, at q = 256 and degree 32).  Every decode entry point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and
  * extrinsic), fixed_iters, poll_every and the active list, the transmitter, channel and error count work unchanged on such a decoder.
  * nbl_read_state returns post, c2v and v2c as on the corresponding log-QSPA decoder; nbl_get_layers works on the layered kind and is
  * NBL_ERR_ARG on the flooding kind.  Method 1 through nbl_create stays the exact log-QSPA. */
 #define NBL_FHT_FLOOR_LOG2 40
 #define NBL_FHT_LAYERED 1u
+#define NBL_FHT_MAX_CHECK_DEGREE 32
 nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                           const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 

@@ -194,7 +194,8 @@ def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=No
                force_generic=0, record_state=False, fht=False):
     """The check-node kernel a decoder of this description would run (nbl_debug_plan; host arithmetic, no device, no decoder):
     (kernel name, fusable, fused, want_v2c).  The description is built the way Decoder builds it; layers / damped / fht as there
-    (None = flooding), force_generic as nbl_debug_force_generic takes it, record_state as nbl_set_record_state."""
+    (None = flooding), force_generic as nbl_debug_force_generic takes it (with fht, 3 names the wide programme, fht_wide /
+    fht_wide_layered, at any check degree), record_state as nbl_set_record_state."""
     lib = load_library()
     params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
     ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
@@ -227,7 +228,8 @@ class Decoder:
     NBL_LAYERED_DAMPED: T-EMS under the layered schedule with its per-edge damping (inert for EMS), False = flags 0.  bp=True (with
     layers, without damped): nbl_create_layered_bp, log-QSPA under the layered schedule with its 0.5 / 0.5 per-edge damping.  fht=True (method 1
     only; without damped, bp, OSD or extension parameters): nbl_create_fht, the FHT sum-product check node in place of the exact one --
-    flooding without layers, the layered schedule of nbl_create_layered_bp with layers="greedy" or an assignment."""
+    flooding without layers, the layered schedule of nbl_create_layered_bp with layers="greedy" or an assignment; the only kind that takes
+    checks above degree 8 (up to NBL_FHT_MAX_CHECK_DEGREE = 32: high-rate codes), with no argument of its own."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,

@@ -119,7 +119,8 @@ extern "C" nbl_status nbl_set_profiling(nbl_decoder *d, int32_t on)
 	return NBL_OK;
 }
 
-// Diagnostic only (not part of include/nbldpc.h): route every shape through the generic kernels.
+// Diagnostic only (not part of include/nbldpc.h): route every shape through the generic kernels (1), the specialised ones without the
+// fused iteration (2); on an nbl_create_fht decoder 3 selects the wide programme (nbl_cn_fht_wide.hip) at any check degree.
 extern "C" nbl_status nbl_debug_force_generic(nbl_decoder *d, int32_t on)
 {
 	if (!d) return NBL_ERR_ARG;
@@ -214,6 +215,7 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_BP_SMALL: HIP_TRY(d, nbl_launch_cn_bp_small(g, w, r, fused, st)); break;
 	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
 	case NBL_CN_FHT: HIP_TRY(d, nbl_launch_cn_fht(g, w, r, st)); break;
+	case NBL_CN_FHT_WIDE: HIP_TRY(d, nbl_launch_cn_fht_wide(g, w, r, st)); break;
 	case NBL_CN_BSTEMS: HIP_TRY(d, nbl_launch_cn_bstems(g, w, r, st)); break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
@@ -268,6 +270,7 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 				case NBL_CN_TEMS_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_BP_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_FHT_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				case NBL_CN_FHT_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				default: d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED;
 				}
 			}

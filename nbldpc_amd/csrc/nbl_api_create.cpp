@@ -406,7 +406,13 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	}
 	const int E = voff[N];
 	if (coff[M] != E) return fail_create(nullptr, NBL_ERR_ARG, "variable-side and check-side edge counts differ");
-	if (maxdc > NBL_MAXDC || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
+	// (nbl_create_fht: the wide programme's storage does not grow with the check degree, so its limit is the LDS block's, 32; the variable
+	// side -- the layer rows, the variable-node pass -- keeps 8 everywhere)
+	if (fht && maxdv <= NBL_MAXDV && maxdc > NBL_FHT_MAX_CHECK_DEGREE)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
+		                                         std::to_string(NBL_FHT_MAX_CHECK_DEGREE) + ")");
+	if ((!fht && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
+	static_assert(NBL_LAYER_ROW >= 4 + NBL_MAXDV, "a layer row holds the c2v slots of every edge of a variable");
 	std::vector<int> v_cpos(E, -1), c_epos(E, -1), c_var(E), c_h(E), c_hinv(E);
 	for (int ce = 0; ce < E; ce++) {
 		int n = code->chk_var[ce], h = code->chk_h[ce];
@@ -440,7 +446,8 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	int n_layers = 0;
 	if (lay) {
 		// (the layered kernel is the general one: no specialised shape stands in for it, so the LDS bound holds for every shape)
-		// (log-QSPA: (3 maxdc + 5) q 8 bytes, at most 59,392 B at q = 256 and degree 8 -- nothing to refuse)
+		// (log-QSPA: (3 maxdc + 5) q 8 bytes, at most 59,392 B at q = 256 and degree 8 -- nothing to refuse; FHT: maxdc q 8 bytes, at most
+		// 65,536 B at q = 256 and degree 32, what a launch gets without opting in -- nothing to refuse either)
 		if (params->method == NBL_METHOD_TEMS) {
 			if (nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");

@@ -33,7 +33,8 @@ __global__ __launch_bounds__(64) void cn_fht_kernel(NblGraphDev g, NblWork w, Nb
 
 hipError_t nbl_launch_cn_fht(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st)
 {
-	// maxdc q 8 bytes: 16 KB at q = 256 and degree 8, the largest the ABI accepts
+	// maxdc q 8 bytes: 16 KB at q = 256 and degree 8, the largest this programme runs (a code with a larger check, up to
+	// NBL_FHT_MAX_CHECK_DEGREE, takes nbl_cn_fht_wide.hip)
 	const size_t lds = nbl_fht_lds_bytes(g.q, g.maxdc);
 	const long long blocks = (long long)r.B * g.M;
 	if (g.maxdc > NBL_MAXDC || lds > 64 * 1024 || blocks > 0x7fffffffLL || !w.v2c) return hipErrorInvalidValue;

@@ -15,7 +15,8 @@
 // other own + partner: the same two roundings as the header's (x[i] + x[i+s], x[i] - x[i+s]).
 //
 // Storage: the transformed inputs U_k stay in registers (DCM x NS doubles per lane; the loops over edges are unrolled over DCM with
-// wave-uniform guards, so no array is indexed dynamically).  LDS holds ONE [maxdc][Q] block of doubles -- at most 16 KB -- which serves
+// wave-uniform guards, so no array is indexed dynamically; degrees above DCM = 8 run the layout of nbl_cn_fht_wide_core.h instead).  LDS
+// holds ONE [maxdc][Q] block of doubles -- at most 16 KB at degree 8 -- which serves
 // three times: the permutation by h_d on the way in, the forward products Fwd_k while the outputs are formed from the last edge down,
 // and the permutation back on the way out (region d is read as Fwd_d by the lane that then overwrites the same slots with c_d).
 // DESIGN.md section 5l has the register report behind that split.

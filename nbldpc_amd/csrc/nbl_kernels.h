@@ -38,9 +38,13 @@ hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, co
 hipError_t nbl_launch_cn_bp_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
 // FHT sum-product check node (nbl_create_fht; nbl_cn_fht.hip flooding, nbl_cn_fht_layered.hip the checks of one layer): the programme of
-// nbl_cn_fht_core.h on the inputs of nbl_cn_bp_inputs.h.  LDS: maxdc q 8 bytes, at most 16 KB
+// nbl_cn_fht_core.h on the inputs of nbl_cn_bp_inputs.h, checks up to degree NBL_MAXDC.  LDS: maxdc q 8 bytes, at most 16 KB
 hipError_t nbl_launch_cn_fht(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_fht_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+// the same programme in the degree-independent layout of nbl_cn_fht_wide_core.h (nbl_cn_fht_wide.hip), checks up to degree
+// NBL_FHT_MAX_CHECK_DEGREE.  LDS: maxdc q 8 bytes, at most 64 KB; the check's c2v region holds its forward products until the final store
+hipError_t nbl_launch_cn_fht_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_fht_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
 // specialised EMS check node (nbl_cn_ems256.hip)
 size_t nbl_ems256_lds_bytes(int nm);

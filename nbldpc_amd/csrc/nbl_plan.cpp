@@ -32,7 +32,7 @@ NblShape nbl_shape(const nbl_code_desc *code)
 
 static const char *const cn_names[NBL_CN_COUNT] = {
 	"ems256", "ems_small", "ems64", "ems", "tems64", "tems256", "tems_small", "tems", "bp256", "bp64", "bp_small", "bp",
-	"bstems", "ems_layered", "tems_layered", "none", "bp_layered", "fht", "fht_layered"};
+	"bstems", "ems_layered", "tems_layered", "none", "bp_layered", "fht", "fht_layered", "fht_wide", "fht_wide_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 
@@ -40,8 +40,11 @@ NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext 
                  bool small_on, bool fht)
 {
 	NblPlan pl{NBL_CN_NONE, false, false, true};
-	if (fht) { // one general kernel per schedule: never fused, no debug switch moves it; both schedules read v2c (flooding: the inputs)
-		pl.cn = layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT;
+	if (fht) { // one general kernel per schedule and layout: never fused; both schedules read v2c (flooding: the inputs)
+		// the register programme holds DCM = NBL_MAXDC transformed inputs per lane; a code with a larger check takes the wide one.
+		// Debug switches 0, 1, 2 move nothing; 3 selects the wide programme at any degree
+		const bool wide = s.maxdc > NBL_MAXDC || force_generic == 3;
+		pl.cn = wide ? (layered ? NBL_CN_FHT_WIDE_LAYERED : NBL_CN_FHT_WIDE) : (layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT);
 		return pl;
 	}
 	if (layered) { // one c2v buffer updated in place: never fused; T-EMS and log-QSPA keep the v2c their damping reads
