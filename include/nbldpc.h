@@ -294,6 +294,30 @@ nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_m
 nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                           const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 
+/* ---- EMS decoding for high-rate codes: check degrees up to 32, flooding and layered ------------------------------------------------
+ * nbl_create_ems_wide: NBL_METHOD_EMS only (no OSD, no extension parameters).  There is no new arithmetic: a check's output is the
+ * canonical, residue-free EMS value defined above (the maximum over conf(q,1) U conf(nm,nc) of the left-to-right sums over the other
+ * edges in index order), which is generic in the check degree; post, c2v, decisions, flags and iteration counts equal the canonical
+ * oracle's bit for bit at every degree.
+ *   flags 0: word for word the flooding EMS decoder of nbl_create (a non-NULL layer_of is NBL_ERR_ARG).  NBL_EMS_WIDE_LAYERED: word for
+ *   word the schedule of nbl_create_layered -- the same layer rules and refusal texts, nbl_layer_greedy for layer_of == NULL.  An unknown
+ *   flag bit is NBL_ERR_ARG.
+ *   Limits: check degrees 2 .. 32 (NBL_EMS_MAX_CHECK_DEGREE; a larger check is NBL_ERR_ARG, the message names this entry point, the degree
+ *   found and 32); variable degrees stay 1 .. 8, with nbl_create's text.  Any other method is NBL_ERR_UNSUPPORTED (the message names
+ *   method 2).  A check is run by one workgroup whose LDS holds [maxdc][q] inputs, the lists [maxdc][nm] (12 bytes an entry), three
+ *   [layers][q] DP arrays (layers = nc + 1, or 1 when nc >= maxdc - 1) and one [q] vector; a shape that needs more than 160 KB is
+ *   NBL_ERR_UNSUPPORTED and the message names the byte count (nm = q = 256 at degree 32 is one).  Everything else nbl_create refuses is
+ *   refused the same way; all of it before the device is touched.
+ *   A code whose checks all have degree 8 or less gets exactly the decoder nbl_create / nbl_create_layered would make.  Every decode entry
+ *   point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the
+ *   active list, the transmitter, channel and error count work unchanged on such a decoder.  nbl_read_state returns post and c2v as on the
+ *   corresponding EMS decoder (a non-NULL v2c is refused on the layered kind, as there); nbl_get_layers works on the layered kind.
+ *   Every other entry point but nbl_create_fht keeps its check-degree limit of 8. */
+#define NBL_EMS_MAX_CHECK_DEGREE 32
+#define NBL_EMS_WIDE_LAYERED 1u
+nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                               const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the
  * reference's return value).  iters: [B] iteration of the first zero syndrome, or max_iter.

@@ -246,7 +246,7 @@ struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out,
-                              bool fht = false);
+                              bool fht = false, bool ems_wide = false);
 
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
@@ -291,6 +291,22 @@ extern "C" nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_FHT_LAYERED) ? &lay : nullptr, device, out, true);
 }
 
+// EMS with check degrees up to NBL_EMS_MAX_CHECK_DEGREE (include/nbldpc.h): flooding without a LayerReq, layered with the request of
+// nbl_create_layered -- the same assignment rules, no v2c state
+extern "C" nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                          const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	if (!out) return NBL_ERR_ARG;
+	*out = nullptr;
+	if (flags & ~(uint32_t)NBL_EMS_WIDE_LAYERED)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_EMS_WIDE_LAYERED = 1 is the only one defined)");
+	if (!(flags & NBL_EMS_WIDE_LAYERED) && layer_of)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or "
+		                                         "set NBL_EMS_WIDE_LAYERED)");
+	const LayerReq lay = {layer_of, 0, false};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_EMS_WIDE_LAYERED) ? &lay : nullptr, device, out, false, true);
+}
+
 extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
 {
 	if (!d || !d->layered) return NBL_ERR_ARG;
@@ -300,7 +316,7 @@ extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, in
 }
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
-                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht)
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht, bool ems_wide)
 {
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
@@ -317,6 +333,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (fht && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_fht runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, "
 		                                                 "which no other method's check node is");
+	if (ems_wide && params->method != NBL_METHOD_EMS)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide runs EMS (method 2) only: the other methods keep their entry points and their check-degree "
+		                                                 "limit of 8 (log-QSPA above it: nbl_create_fht)");
 	if (lay && lay->bp && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_layered_bp runs log-QSPA (method 1) only: the layered schedule of EMS (method 2) is behind "
 		                                                 "nbl_create_layered, that of T-EMS (method 4) behind nbl_create_layered_ex with NBL_LAYERED_DAMPED");
@@ -411,7 +430,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (fht && maxdv <= NBL_MAXDV && maxdc > NBL_FHT_MAX_CHECK_DEGREE)
 		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
 		                                         std::to_string(NBL_FHT_MAX_CHECK_DEGREE) + ")");
-	if ((!fht && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
+	// (nbl_create_ems_wide: one workgroup per check, no array sized by the degree; the limit is the header's, the LDS bound is checked below)
+	if (ems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_EMS_MAX_CHECK_DEGREE)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
+		                                         std::to_string(NBL_EMS_MAX_CHECK_DEGREE) + ")");
+	if ((!fht && !ems_wide && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
 	static_assert(NBL_LAYER_ROW >= 4 + NBL_MAXDV, "a layer row holds the c2v slots of every edge of a variable");
 	std::vector<int> v_cpos(E, -1), c_epos(E, -1), c_var(E), c_h(E), c_hinv(E);
 	for (int ce = 0; ce < E; ce++) {
@@ -439,8 +462,13 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	// shape limits of the kernels, refused here rather than at the first decode
 	if (params->method == NBL_METHOD_TEMS && p * maxdc > 32)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: log2(q) * (largest check degree) must not exceed 32 (the trellis path code is one 32-bit word)");
-	if (params->method == NBL_METHOD_EMS && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024)
+	// (a wide decoder with maxdc <= NBL_MAXDC may run either programme: both bounds hold, the general kernel's first, with nbl_create's text)
+	if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
+	if (ems_wide && nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > NBL_EMS_WIDE_MAX_LDS)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide: this (q, check degree, nm, nc) needs " +
+		                                                 std::to_string(nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc)) +
+		                                                 " bytes of LDS per check, more than the 160 KB (163840 bytes) one workgroup can have");
 	// ---- layered schedule: the assignment, checked or made here, before the device is touched ----
 	std::vector<int> layer_of, lay_off, lay_chk, lay_nbr;
 	int n_layers = 0;
@@ -451,7 +479,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		if (params->method == NBL_METHOD_TEMS) {
 			if (nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");
-		} else if (params->method == NBL_METHOD_EMS && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
+		} else if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
 			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
 		}
 		layer_of.assign(M, 0);
@@ -516,6 +544,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		d->h_lay_off = lay_off;
 	}
 	d->fht = fht;
+	d->ems_wide = ems_wide;
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;

@@ -32,14 +32,24 @@ NblShape nbl_shape(const nbl_code_desc *code)
 
 static const char *const cn_names[NBL_CN_COUNT] = {
 	"ems256", "ems_small", "ems64", "ems", "tems64", "tems256", "tems_small", "tems", "bp256", "bp64", "bp_small", "bp",
-	"bstems", "ems_layered", "tems_layered", "none", "bp_layered", "fht", "fht_layered", "fht_wide", "fht_wide_layered"};
+	"bstems", "ems_layered", "tems_layered", "none", "bp_layered", "fht", "fht_layered", "fht_wide", "fht_wide_layered", "ems_wide", "ems_wide_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht)
+                 bool small_on, bool fht, bool ems_wide)
 {
 	NblPlan pl{NBL_CN_NONE, false, false, true};
+	if (ems_wide && (s.maxdc > NBL_MAXDC || force_generic == 3)) {
+		// the workgroup-per-check programme: never fused.  Flooding reads the v2c of the variable-node pass; layered forms its inputs from
+		// L_ch and c2v.  With maxdc <= NBL_MAXDC (switch 3) `fusable` -- which buffers the workspace holds -- stays that of the decoder's
+		// default plan (switch 0), so that the workspace does not move with a debug switch
+		if (s.maxdc <= NBL_MAXDC) pl.fusable = nbl_plan(s, prm, nbl_params_ext{}, layered, 0, record_state, small_on).fusable;
+		pl.cn = layered ? NBL_CN_EMS_WIDE_LAYERED : NBL_CN_EMS_WIDE;
+		pl.fused = false;
+		pl.want_v2c = !layered;
+		return pl;
+	}
 	if (fht) { // one general kernel per schedule and layout: never fused; both schedules read v2c (flooding: the inputs)
 		// the register programme holds DCM = NBL_MAXDC transformed inputs per lane; a code with a larger check takes the wide one.
 		// Debug switches 0, 1, 2 move nothing; 3 selects the wide programme at any degree

@@ -12,6 +12,7 @@ enum NblCn {
 	NBL_CN_BP_LAYERED,
 	NBL_CN_FHT, NBL_CN_FHT_LAYERED, // nbl_create_fht: the FHT sum-product check node, flooding and layered
 	NBL_CN_FHT_WIDE, NBL_CN_FHT_WIDE_LAYERED, // the same in the degree-independent layout: codes with a check above degree NBL_MAXDC
+	NBL_CN_EMS_WIDE, NBL_CN_EMS_WIDE_LAYERED, // nbl_create_ems_wide: EMS, one check per workgroup, any check degree up to NBL_EMS_MAX_CHECK_DEGREE
 	NBL_CN_COUNT
 };
 
@@ -26,9 +27,11 @@ NblShape nbl_shape(const nbl_code_desc *code);
 // force_generic: nbl_debug_force_generic's value (1 = the general kernel, 2 = the specialised one, neither fused);
 // small_on: the kernels NBL_NO_SMALL switches off (EMS-small, T-EMS-small, BP-small, EMS-64) may be chosen;
 // fht: an nbl_create_fht decoder (method 1; `layered` says which of its two schedules); there force_generic 3 selects the wide
-// programme at any check degree (so that the two layouts can be compared on the same inputs) and 0, 1, 2 change nothing
+// programme at any check degree (so that the two layouts can be compared on the same inputs) and 0, 1, 2 change nothing;
+// ems_wide: an nbl_create_ems_wide decoder (method 2): a code with a check above degree NBL_MAXDC runs ems_wide / ems_wide_layered under
+// every switch; any other code gets the plan of nbl_create / nbl_create_layered, except that force_generic 3 selects the wide programme
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht = false);
+                 bool small_on, bool fht = false, bool ems_wide = false);
 const char *nbl_cn_name(NblCn cn);
 
 // What each specialised kernel can run, beside the kernel (its LDS arithmetic lives there); nbl_plan is the only caller.

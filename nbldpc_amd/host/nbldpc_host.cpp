@@ -129,7 +129,22 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = fht       ? nbl_create_fht(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT_LAYERED : 0u, device, &dec)
+	// NBL_EMS_WIDE=1: EMS through nbl_create_ems_wide, which takes check degrees up to NBL_EMS_MAX_CHECK_DEGREE (off by default, NBL_EMS_WIDE=0
+	// names the default).  An EMS profile (method 2) without OSD only; combines with NBL_SCHEDULE=flooding (or unset) and layered
+	const char *wenv = getenv("NBL_EMS_WIDE");
+	const bool wide = wenv && std::string(wenv) == "1";
+	if (wenv && !wide && std::string(wenv) != "0") {
+		error = std::string("NBL_EMS_WIDE=") + wenv + ": unknown value (0, 1)";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (wide && (sim.decodeMethod != EMS_DECODE || osd || damped || lay_bp)) {
+		error = "NBL_EMS_WIDE=1: the wide EMS decoder is defined for EMS (method 2) without OSD only, under NBL_SCHEDULE=flooding or layered";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	nbl_status st = wide      ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)
+	                : fht     ? nbl_create_fht(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT_LAYERED : 0u, device, &dec)
 	                : lay_bp  ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
 	                : damped  ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
 	                : layered ? nbl_create_layered(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
