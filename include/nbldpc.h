@@ -645,7 +645,11 @@ nbl_status nbl_set_record_state(nbl_decoder *dec, int32_t on);
 
 /* Per-phase device time of the last decode call in milliseconds (HIP events on the launch stream):
  * ms[0] variable-node kernels, ms[1] syndrome kernels, ms[2] check-node kernels, ms[3] whole call.
- * Only filled when profiling was switched on with nbl_set_profiling(dec, 1). */
+ * Only filled when profiling was switched on with nbl_set_profiling(dec, 1).
+ * launches[0..2]: variable-node, syndrome and check-node launches of the last decode call.  Undamped fused EMS leaves the check-node
+ * pass of iteration max_iter, which no output of the call depends on, to the first nbl_read_state / nbl_soft_output* that asks for
+ * the messages: a profiled call counts the launches its times cover (max_iter - 1 until that pass has run), an unprofiled one the
+ * passes of its schedule (max_iter). */
 nbl_status nbl_set_profiling(nbl_decoder *dec, int32_t on);
 nbl_status nbl_last_timing(nbl_decoder *dec, double ms[4], int64_t launches[3]);
 

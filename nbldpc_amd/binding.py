@@ -608,6 +608,12 @@ class Decoder:
     def record_state(self, on=True):
         self._chk(self.lib.nbl_set_record_state(self.h, int(on)))
 
+    def defer_last(self, on=True):
+        """diagnostic (nbl_debug_defer_last): False = every decode runs the check-node pass of its last iteration itself; True (the
+        default) = undamped fused EMS leaves it to the first read of the message state"""
+        self.lib.nbl_debug_defer_last.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(self.lib.nbl_debug_defer_last(self.h, int(on)))
+
     def profiling(self, on=True):
         self._chk(self.lib.nbl_set_profiling(self.h, int(on)))
 

@@ -13,6 +13,7 @@ static void drop_graphs(nbl_decoder *d)
 	for (auto &ge : d->gexec)
 		if (ge) (void)hipGraphExecDestroy(ge);
 	d->gexec.clear();
+	d->pending.on = false; // (the buffers a pending pass names go with what is dropped here: it is never run late)
 }
 
 static void free_workspace(nbl_decoder *d)
@@ -108,6 +109,7 @@ extern "C" void nbl_destroy(nbl_decoder *d)
 	for (auto &e : d->ev)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &e : d->pev) (void)hipEventDestroy(e);
+	if (d->pending_ev) (void)hipEventDestroy(d->pending_ev);
 	if (d->stream) (void)hipStreamDestroy(d->stream);
 	delete d; // (every buffer the handle owns is freed by its DevBuf)
 }
@@ -160,6 +162,15 @@ extern "C" nbl_status nbl_debug_stamps(nbl_decoder *d, int32_t on, unsigned long
 	return NBL_OK;
 }
 
+// Diagnostic only (not part of include/nbldpc.h): 0 = every decode runs the check-node pass of its last iteration itself, 1 (the
+// default) = undamped fused EMS leaves it to the first reader of the message state (finish_pending).  Tests and A/B runs compare both.
+extern "C" nbl_status nbl_debug_defer_last(nbl_decoder *d, int32_t on)
+{
+	if (!d) return NBL_ERR_ARG;
+	d->defer_last = on != 0;
+	return NBL_OK;
+}
+
 extern "C" nbl_status nbl_set_record_state(nbl_decoder *d, int32_t on)
 {
 	if (!d) return NBL_ERR_ARG;
@@ -172,6 +183,10 @@ extern "C" nbl_status nbl_last_timing(nbl_decoder *d, double ms[4], int64_t laun
 	if (!d) return NBL_ERR_ARG;
 	if (ms) memcpy(ms, d->ms, sizeof d->ms);
 	if (launches) for (int i = 0; i < 3; i++) launches[i] = d->launches[i];
+	// A check-node pass the decode left pending (finish_pending): a profiled call counts the launches its times cover, so that
+	// ms[2] / launches[2] stays the time of one launch -- the pass is counted when it runs.  Without profiling the counters describe
+	// the call's schedule, one check-node pass per iteration, run by now or owed.
+	if (launches && d->pending.on && !d->pending.timed) launches[2]++;
 	return NBL_OK;
 }
 
@@ -250,6 +265,7 @@ struct IterCtx {
 	double *bufA, *bufB;
 	const double *zeros = nullptr; // stands in for bufA in iteration 1 (then bufA needs no clearing)
 	int batch = 0;                 // codewords of the call (r.B may shrink to the active list; the OSD sums cover every codeword)
+	bool defer = false;            // iteration max_iter runs its variable-node half alone (defers_last)
 	// profiling: one event after every launch on the launch stream; phase time = sum of the gaps it closes
 	size_t nev = 0;
 	std::vector<int> tag; // 0 vn, 1 syn, 2 cn, 3 other
@@ -262,6 +278,15 @@ static hipError_t mark(IterCtx &c, int t, hipStream_t st)
 	if (c.nev == d->pev.size()) { hipEvent_t e; hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; d->pev.push_back(e); }
 	c.tag.push_back(t);
 	return hipEventRecord(d->pev[c.nev++], st);
+}
+
+// Whether the decode leaves the check-node half of iteration max_iter to finish_pending.  Nothing a decode returns depends on that
+// pass: its c2v would be read by an iteration max_iter + 1 that never runs.  Undamped fused EMS only -- the damped fused kernels keep
+// per-edge decision and v2c state in their variable-node stage -- and only while nothing records or accumulates per iteration.
+static bool defers_last(const nbl_decoder *d, const NblPlan &plan)
+{
+	return d->defer_last && plan.fused && d->prm.method == NBL_METHOD_EMS && d->prm.max_iter >= 2 && !d->layered && !d->record_state &&
+	       !d->osd_acc && !d->osd_on && !d->w.post && !d->w.stamps;
 }
 
 // launches of iterations it_lo .. it_hi on `st`
@@ -295,6 +320,19 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			if (count) { d->launches[0]++; d->launches[1]++; d->launches[2] += d->n_layers; }
 			continue;
 		}
+		if (c.plan.fused && c.defer && it == d->prm.max_iter) {
+			// the last iteration: posterior and decision from the c2v of iteration max_iter - 1 (the layered schedule's pass: the same
+			// sums in the same order, the same decision rule), then the syndrome.  Tagged "other": no time is variable-node time on
+			// the fused path.
+			NblWork wv = d->w;
+			wv.c2v = (it & 1) ? c.bufA : c.bufB;
+			HIP_TRY(d, nbl_launch_vn_decide(d->g, wv, c.r, st));
+			HIP_TRY(d, mark(c, 3, st));
+			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
+			HIP_TRY(d, mark(c, 1, st));
+			if (count) d->launches[1]++;
+			continue;
+		}
 		if (c.plan.fused) {
 			// one launch = variable-node pass + check-node pass; c2v ping-pongs between the two buffers
 			NblWork wf = d->w;
@@ -324,7 +362,8 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 		HIP_TRY(d, mark(c, 1, st));
 		if (count) { d->launches[0]++; d->launches[1]++; }
 		// (the reference leaves the loop after the syndrome check of the last iteration it runs; the check-node pass of a
-		// window's last iteration is only needed if another window follows -- it is cheap to keep the windows uniform)
+		// window's last iteration is only needed if another window follows.  It is not cheap -- one check-node launch per call --
+		// and the fused EMS path above defers it; here c2v is updated in place and nbl_read_state returns it, so it stays)
 		const nbl_status s = launch_cn(d, c.plan.cn, d->w, c.r, false, st);
 		if (s) return s;
 		HIP_TRY(d, mark(c, 2, st));
@@ -358,6 +397,7 @@ static nbl_status run_window(IterCtx &c, int widx, int it_lo, int it_hi, hipStre
 			HIP_TRY(d, hipGraphLaunch(d->gexec[widx], st));
 			const int n = it_hi - it_lo + 1;
 			d->launches[1] += n; d->launches[2] += d->layered ? (long long)n * d->n_layers : n;
+			if (c.defer && it_hi == d->prm.max_iter) d->launches[2]--; // (the captured window holds the deferred form)
 			if (!c.plan.fused) d->launches[0] += n;
 			return NBL_OK;
 		}
@@ -370,6 +410,7 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 	const nbl_params &p = d->prm;
 	IterCtx c;
 	c.d = d;
+	d->pending.on = false; // (a pass the last decode left pending is dropped: nobody read that state)
 	d->idd_sub = false; // (the loop sets it again after its last pass)
 	c.damp = p.method != NBL_METHOD_EMS;
 	NblRun &r = c.r;
@@ -386,8 +427,9 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 	c.bufA = d->w.c2v;
 	c.bufB = d->ws.c2v_alt;
 	c.zeros = c.plan.fused ? d->ws.c2v_zero.p : nullptr;
+	c.defer = defers_last(d, c.plan);
 	// the captured graphs hold buffer addresses and the batch size: any change drops them
-	const nbl_decoder::GraphKey key = {d_Lin, d->w.Lch, d->w.v2c, d->w.c2v, d->ws.c2v_alt, d->w.post, d->ws.osd_S, B, d->record_state ? 1 : 0, d->force_generic, c.plan.fused ? 1 : 0};
+	const nbl_decoder::GraphKey key = {d_Lin, d->w.Lch, d->w.v2c, d->w.c2v, d->ws.c2v_alt, d->w.post, d->ws.osd_S, B, d->record_state ? 1 : 0, d->force_generic, c.plan.fused ? (c.defer ? 3 : 1) : 0};
 	c.batch = B;
 	if (memcmp(&key, &d->gkey, sizeof key) != 0) { drop_graphs(d); d->gkey = key; }
 	HIP_TRY(d, mark(c, 3, st));
@@ -441,6 +483,27 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 	}
 	if (polling) HIP_TRY(d, hipStreamSynchronize(st));
 	if (c.plan.fused && last_it > 0) d->last_c2v = (last_it & 1) ? c.bufB : c.bufA;
+	if (c.defer && last_it == p.max_iter) {
+		// iteration max_iter ran without its check-node half: until finish_pending the last c2v is that of iteration max_iter - 1.
+		// The late launch covers the whole batch: under early exit it returns at once for every codeword that is done by now.
+		nbl_decoder::Pending &pd = d->pending;
+		pd.iter = last_it;
+		pd.prev = (last_it & 1) ? c.bufA : c.bufB;
+		pd.out = (last_it & 1) ? c.bufB : c.bufA;
+		pd.batch = B;
+		pd.cn = c.plan.cn;
+		pd.r = c.r;
+		pd.r.iter = last_it;
+		pd.r.B = B;
+		pd.timed = d->profiling;
+		pd.foreign = st != d->stream;
+		if (pd.foreign) {
+			if (!d->pending_ev) HIP_TRY(d, hipEventCreateWithFlags(&d->pending_ev, hipEventDisableTiming));
+			HIP_TRY(d, hipEventRecord(d->pending_ev, st));
+		}
+		d->last_c2v = pd.prev;
+		pd.on = true;
+	}
 	if (d->profiling && c.nev > 0) {
 		HIP_TRY(d, hipEventSynchronize(d->pev[c.nev - 1]));
 		d->ms[0] = d->ms[1] = d->ms[2] = d->ms[3] = 0;
@@ -452,6 +515,31 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 		}
 	}
 	d->last_B = B;
+	return NBL_OK;
+}
+
+nbl_status finish_pending(nbl_decoder *d, hipStream_t reader)
+{
+	nbl_decoder::Pending &pd = d->pending;
+	if (!pd.on) return NBL_OK;
+	// exactly the fused launch the decode skipped: L_ch and the c2v of iteration max_iter - 1 are intact until the next decode, and the
+	// launch rewrites dec with the values the variable-node pass left there
+	if (pd.foreign) HIP_TRY(d, hipStreamWaitEvent(d->stream, d->pending_ev, 0));
+	NblWork wf = d->w;
+	wf.active = nullptr;
+	wf.c2v_prev = pd.prev;
+	wf.c2v_prev_shared = 0;
+	wf.c2v = pd.out;
+	wf.store_v2c = 0;
+	if (const nbl_status s = launch_cn(d, pd.cn, wf, pd.r, true, d->stream)) return s;
+	d->last_c2v = pd.out;
+	d->launches[2]++; // (with pd.on cleared below nbl_last_timing stops adding the owed pass: the count moves only for a profiled call)
+	pd.on = false;
+	if (reader && reader != d->stream) {
+		if (!d->pending_ev) HIP_TRY(d, hipEventCreateWithFlags(&d->pending_ev, hipEventDisableTiming));
+		HIP_TRY(d, hipEventRecord(d->pending_ev, d->stream));
+		HIP_TRY(d, hipStreamWaitEvent(reader, d->pending_ev, 0));
+	}
 	return NBL_OK;
 }
 
@@ -539,6 +627,7 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 		else if (!d->w.v2c) { d->err = "v2c is not kept in HBM on the fused path unless state recording is on (nbl_set_record_state)"; rc = NBL_ERR_ARG; }
 		else rc = grab(d->w.v2c + (size_t)b * E * q, nullptr, E, v2c);
 	}
+	if (!rc && c2v) rc = finish_pending(d);
 	if (!rc && c2v) {
 		const double *src = d->last_c2v ? d->last_c2v : d->w.c2v;
 		if (d->last_fused && d->ws.c2v_alt && !d->prm.fixed_iters) {

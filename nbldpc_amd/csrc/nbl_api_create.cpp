@@ -518,6 +518,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) return fail_create(d, NBL_ERR_HIP, "hipStreamCreate failed");
 	if (const char *e = getenv("NBL_GRAPH")) d->use_graph = atoi(e) != 0;
 	if (const char *e = getenv("NBL_COMPACT")) d->use_compact = atoi(e) != 0;
+	if (const char *e = getenv("NBL_DEFER_LAST")) d->defer_last = atoi(e) != 0;
 	d->g.N = N; d->g.M = M; d->g.E = E; d->g.q = q; d->g.p = p; d->g.poly = poly; d->g.maxdc = maxdc; d->g.maxdv = maxdv;
 	std::vector<uint8_t> mul8((size_t)q * q);
 	for (size_t i = 0; i < mul8.size(); i++) mul8[i] = (uint8_t)gf_mul[i];

@@ -53,6 +53,22 @@ struct nbl_decoder {
 	NblShape shape{};           // what the kernel choice depends on (nbl_plan.h)
 	const double *last_c2v = nullptr;
 	bool last_fused = false;    // the last decode ran fused iterations (nbl_read_state picks the c2v buffer per codeword)
+	// The check-node half of iteration max_iter, which only a reader of the message state needs (undamped fused EMS; DESIGN.md section
+	// 4): the decode ran that iteration's variable-node pass alone (vn_decide on the c2v of iteration max_iter - 1) and left the fused
+	// launch to finish_pending.  Dropped, not run, by the next decode and wherever the workspace or the graphs go.
+	struct Pending {
+		bool on = false;
+		bool timed = false;           // the decode was profiled: nbl_last_timing counts the launches its times cover, not the owed pass
+		bool foreign = false;         // the decode ran on a caller's stream: pending_ev marks its end there
+		int iter = 0;                 // = max_iter
+		const double *prev = nullptr; // c2v of iteration iter - 1 (read)
+		double *out = nullptr;        // c2v of iteration iter (written)
+		int batch = 0;
+		NblCn cn{};
+		NblRun r{};                   // as the skipped launch would have had it, B = batch
+	} pending;
+	hipEvent_t pending_ev = nullptr; // made by the first decode on a caller's stream that defers
+	bool defer_last = true;          // nbl_debug_defer_last; NBL_DEFER_LAST=0 makes handles with it off
 	// layered (check-serial) schedule (nbl_create_layered / nbl_create_layered_ex / nbl_create_layered_bp): one c2v buffer updated in
 	// place; EMS keeps no v2c, T-EMS (NBL_LAYERED_DAMPED) and log-QSPA keep the per-edge v2c their damping reads, updated in place by the
 	// edge's check
@@ -189,6 +205,9 @@ inline const char *const NBL_IDD_SUB_TEXT = ": the last decode call was an itera
 extern thread_local std::string g_create_error; // what nbl_last_error(NULL) reports
 nbl_status ensure_workspace(nbl_decoder *d, int B);
 nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_t st);
+// Runs the deferred check-node pass of the last decode, if one is pending, on d->stream; every reader of the last c2v calls it first.
+// reader: the stream that will read the c2v (NULL or d->stream: nothing more to order).
+nbl_status finish_pending(nbl_decoder *d, hipStream_t reader = nullptr);
 // The results of a decode call, B codewords from out / done / iters (the workspace's, or the loop's at batch positions), to the
 // caller's arrays on `st`; to_done and to_iters may be NULL.  sync: wait for the stream afterwards (the host forms).
 nbl_status read_back(nbl_decoder *d, const int *out, const uint8_t *done, const int *iters, int B, int32_t *to_out, uint8_t *to_done,

@@ -16,16 +16,17 @@
 // (NBLDPC.cpp:649-662 / 781-794 / 934-969)
 // ---------------------------------------------------------------------------------------------------------
 // write_v2c bit 0: also v2c = L_ch (damped methods read it); bit 1: leave c2v alone (fused iterations read the zeros of
-// iteration 0 from a buffer of their own)
+// iteration 0 from a buffer of their own); bit 2: L_ch is already padded (init_rows_kernel)
 __global__ void init_kernel(const double *__restrict__ Lin, NblGraphDev g, NblWork w, int B, int write_v2c)
 {
 	const int q = g.q;
 	long long total = (long long)B * g.N * q;
-	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-		int a = (int)(i % q);
-		long long bn = i / q;
-		if (Lin) w.Lch[i] = a ? Lin[bn * (q - 1) + (a - 1)] : 0.0; // else: demod_kernel has already filled Lch
-	}
+	if (Lin && !(write_v2c & 4)) // else: demod_kernel or init_rows_kernel has already filled Lch
+		for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+			int a = (int)(i % q);
+			long long bn = i / q;
+			w.Lch[i] = a ? Lin[bn * (q - 1) + (a - 1)] : 0.0;
+		}
 	long long etotal = (long long)B * g.E * q;
 	if (!(write_v2c & 2))
 		for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < etotal; i += (long long)gridDim.x * blockDim.x)
@@ -47,6 +48,51 @@ __global__ void init_kernel(const double *__restrict__ Lin, NblGraphDev g, NblWo
 		w.iters[i] = 0;
 	}
 	if (blockIdx.x == 0 && threadIdx.x == 0) *w.n_done = 0;
+}
+
+// The L_ch part of init for q >= 64, row by row: Q / 2 lanes (at most a wave) take one (codeword, variable) row, each lane two
+// neighbouring symbols per pass -- 8-byte loads (a [q-1] row is only 8-byte aligned), one 16-byte store, slot 0 = 0.0 -- and a wave
+// carries ROWS such row groups with every load issued before the first store.  No division per element: the row comes from the wave's
+// index.  flags: 1 = also done / iters / n_done (then init_kernel has nothing left to do on the fused undamped path).
+template <int Q, int ROWS>
+__global__ __launch_bounds__(256) void init_rows_kernel(const double *__restrict__ Lin, double *__restrict__ Lch, long long rows, NblWork w, int B, int flags)
+{
+	constexpr int LPR = (Q / 2 < 64) ? Q / 2 : 64; // lanes per row
+	constexpr int RPW = 64 / LPR;                  // rows side by side in a wave
+	constexpr int P = Q / (2 * LPR);               // passes over a row
+	const int lane = lane_id(), sub = lane / LPR, ll = lane % LPR;
+	const long long wave = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	const long long row0 = wave * (ROWS * RPW) + sub;
+	double2 val[ROWS][P];
+#pragma unroll
+	for (int k = 0; k < ROWS; k++) {
+		const long long row = row0 + (long long)k * RPW;
+		if (row < rows) {
+			const double *src = Lin + (size_t)row * (Q - 1);
+#pragma unroll
+			for (int p = 0; p < P; p++) {
+				const int a = 2 * ll + 2 * LPR * p; // symbols a, a + 1 <= Q - 1
+				val[k][p].x = a ? src[a - 1] : 0.0;
+				val[k][p].y = src[a];
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < ROWS; k++) {
+		const long long row = row0 + (long long)k * RPW;
+		if (row < rows) {
+			double2 *dst = (double2 *)(Lch + (size_t)row * Q);
+#pragma unroll
+			for (int p = 0; p < P; p++) dst[ll + LPR * p] = val[k][p];
+		}
+	}
+	if (flags & 1) {
+		for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < B; i += (long long)gridDim.x * blockDim.x) {
+			w.done[i] = 0;
+			w.iters[i] = 0;
+		}
+		if (blockIdx.x == 0 && threadIdx.x == 0) *w.n_done = 0;
+	}
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -327,6 +373,24 @@ __global__ void unpad_kernel(const double *__restrict__ src, double *__restrict_
 
 hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblWork &w, int B, int write_v2c, hipStream_t st)
 {
+	if (d_Lin && g.q >= 64 && B > 0) {
+		// the re-pad at copy speed; with nothing else to initialise but the flags (fused undamped iterations) that is the whole init
+		constexpr int ROWS = 4;
+		const long long rows = (long long)B * g.N;
+		const int rpw = g.q >= 128 ? 1 : 128 / g.q;
+		const long long waves = (rows + ROWS * rpw - 1) / (ROWS * rpw), rblocks = (waves + 3) / 4;
+		if (rblocks > 0x7fffffffLL) return hipErrorInvalidValue;
+		const bool whole = write_v2c == 2;
+		dim3 rgrid((unsigned)rblocks), rblock(256);
+		switch (g.q) {
+		case 64: init_rows_kernel<64, ROWS><<<rgrid, rblock, 0, st>>>(d_Lin, w.Lch, rows, w, B, whole ? 1 : 0); break;
+		case 128: init_rows_kernel<128, ROWS><<<rgrid, rblock, 0, st>>>(d_Lin, w.Lch, rows, w, B, whole ? 1 : 0); break;
+		case 256: init_rows_kernel<256, ROWS><<<rgrid, rblock, 0, st>>>(d_Lin, w.Lch, rows, w, B, whole ? 1 : 0); break;
+		default: return hipErrorInvalidValue;
+		}
+		if (whole) return hipGetLastError();
+		write_v2c |= 4;
+	}
 	long long total = (long long)B * g.E * g.q;
 	int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
 	if (blocks < 1) blocks = 1;
