@@ -16,8 +16,8 @@
 //     holds the nm-th best value; if that bucket ends exactly at the nm-th entry the members are known, otherwise a ballot
 //     quickselect inside the bucket finds the exact cut under SortLLRVector's order (value desc, higher symbol first
 //     among equals).
-//   * wave maxima / minima are reduced on order-preserving 32-bit keys (one DPP instruction per step); the lane that holds
-//     the maximum key delivers the exact FP64 value.
+//   * wave maxima / minima are reduced on order-preserving 32-bit keys (one DPP instruction per step, the four edges' reductions
+//     side by side); the lane that holds the maximum key delivers the exact FP64 value.
 //   * conf(nm, nc >= 3): the three pair convolutions e0(+)e1, e0(+)e2, e1(+)e2 are scattered in one pass into three LDS
 //     buffers; the outputs 2, 1, 0 all gather over the list of edge 3 and share one loop (one broadcast read of the list
 //     entry and one address per entry serve three convolutions).
@@ -28,6 +28,9 @@
 #endif
 #ifndef NBL_EMS_ND
 #define NBL_EMS_ND 1 // short-list checks on which at most one edge can still deviate go straight to the emit stage (0: they run the short-list code, for A/B runs)
+#endif
+#ifndef NBL_EMS_TRIMS
+#define NBL_EMS_TRIMS 13 // wave-uniform work taken off the vector ALU, one bit per item (for A/B runs): 1 packed gather offsets, 4 lmin only in front of the histogram, 8 nd == 0 from four compares
 #endif
 #include <type_traits>
 #include "nbl_device.h"
@@ -81,8 +84,8 @@ __device__ __forceinline__ int wave_scan_add(int x)
 	return x;
 }
 
-// wave max / min of 32-bit integers: with the operation's identity as the DPP `old` value hipcc folds the move into the
-// v_max_i32_dpp / v_min_i32_dpp itself (six instructions per reduction)
+// wave max of 32-bit integers: with the operation's identity as the DPP `old` value hipcc folds the move into the
+// v_max_i32_dpp itself (six instructions per reduction); four at once, max or min: wave_reduce_i32x4 (nbl_device.h)
 __device__ __forceinline__ int wave_max_i32(int x)
 {
 	constexpr int ID = (int)0x80000000;
@@ -93,18 +96,6 @@ __device__ __forceinline__ int wave_max_i32(int x)
 	x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x140, 0xF, 0xF, false));
 	x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x142, 0xA, 0xF, false));
 	x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x143, 0xC, 0xF, false));
-	return __builtin_amdgcn_readlane(x, 63);
-}
-__device__ __forceinline__ int wave_min_i32(int x)
-{
-	constexpr int ID = 0x7fffffff;
-	auto mn = [](int a, int b) { return a < b ? a : b; };
-	x = mn(x, __builtin_amdgcn_update_dpp(ID, x, 0xB1, 0xF, 0xF, false));
-	x = mn(x, __builtin_amdgcn_update_dpp(ID, x, 0x4E, 0xF, 0xF, false));
-	x = mn(x, __builtin_amdgcn_update_dpp(ID, x, 0x141, 0xF, 0xF, false));
-	x = mn(x, __builtin_amdgcn_update_dpp(ID, x, 0x140, 0xF, 0xF, false));
-	x = mn(x, __builtin_amdgcn_update_dpp(ID, x, 0x142, 0xA, 0xF, false));
-	x = mn(x, __builtin_amdgcn_update_dpp(ID, x, 0x143, 0xC, 0xF, false));
 	return __builtin_amdgcn_readlane(x, 63);
 }
 
@@ -431,37 +422,66 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 	double mtop[4], lmin[4];
 	double sec[4] = {0, 0, 0, 0}; // an upper bound of the best value beside rank 0 (for the bounds in front of the gathers)
 	int ztop[4];
-#pragma unroll
-	for (int j = 0; j < 4; j++) {
-		const double loc = dmax(dmax(v[j][0], v[j][1]), dmax(v[j][2], v[j][3]));
-		const int k = key32(loc);
-		mtop[j] = wave_max_exact(loc, k, wave_max_i32(k));
-		// 64 distinct entries are >= the smallest lane maximum, so the nm-th best (nm <= 64) is too; the key of that minimum is
-		// taken one float step down (rounding may have gone up) -- any lower bound will do
-		// (a float infinity must not become the bound: the key is clamped on the scalar unit, below the key of FLT_MAX)
+	// lower bound of the nm-th best value of an edge from the wave minimum of the keys of the lane maxima: 64 distinct entries
+	// are >= the smallest lane maximum, so the nm-th best (nm <= 64) is too; the key of that minimum is taken one float step
+	// down (rounding may have gone up) -- any lower bound will do
+	// (a float infinity must not become the bound: the key is clamped on the scalar unit, below the key of FLT_MAX)
+	auto lmin_of = [](int kmin, double mt) {
 		constexpr int KEY_3E38 = 0x7f61b1e6; // key32(3.0e38)
-		const int kmin = wave_min_i32(k);
 		const double lf = (double)unkey32(kmin < KEY_3E38 ? kmin : KEY_3E38);
-		lmin[j] = ((lf - (mtop[j] - lf) * 0x1p-20) - __builtin_fabs(lf) * 0x1p-22) - 0x1p-120; // (margins: float rounding, rcp in the bucket scale)
-		uint64_t eqm[4];
+		return ((lf - (mt - lf) * 0x1p-20) - __builtin_fabs(lf) * 0x1p-22) - 0x1p-120; // (margins: float rounding, rcp in the bucket scale)
+	};
+	// the wave reductions of the four edges side by side (wave_reduce_i32x4): the maxima of the keys, then -- with the gate on --
+	// the keys beside rank 0
+	{
+		double loc[4];
+		int kj[4], kmax[4], tlj[4], topaj[4];
 #pragma unroll
-		for (int i = 0; i < 4; i++) eqm[i] = __ballot(v[j][i] == mtop[j]);
-		const int topa = highest_sym(eqm); // variable-domain symbol of rank 0
-		const int tl = (topa & 127) >> 1;
-		const unsigned twl = (unsigned)__builtin_amdgcn_readlane((int)toff[j].x, tl), twh = (unsigned)__builtin_amdgcn_readlane((int)toff[j].y, tl);
-		const unsigned tw = (topa & 128) ? twh : twl;
-		ztop[j] = (int)((tw >> (16 * (topa & 1))) & 0xffffu) >> 3;
+		for (int j = 0; j < 4; j++) {
+			loc[j] = dmax(dmax(v[j][0], v[j][1]), dmax(v[j][2], v[j][3]));
+			kmax[j] = kj[j] = key32(loc[j]);
+		}
+		wave_reduce_i32x4<true>(kmax);
+#if !(NBL_EMS_TRIMS & 4)
+		int kmin[4] = {kj[0], kj[1], kj[2], kj[3]};
+		wave_reduce_i32x4<false>(kmin);
+#endif
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			mtop[j] = wave_max_exact(loc[j], kj[j], kmax[j]);
+#if !(NBL_EMS_TRIMS & 4)
+			lmin[j] = lmin_of(kmin[j], mtop[j]);
+#endif
+			uint64_t eqm[4];
+#pragma unroll
+			for (int i = 0; i < 4; i++) eqm[i] = __ballot(v[j][i] == mtop[j]);
+			const int topa = highest_sym(eqm); // variable-domain symbol of rank 0
+			const int tl = (topa & 127) >> 1;
+			const unsigned twl = (unsigned)__builtin_amdgcn_readlane((int)toff[j].x, tl), twh = (unsigned)__builtin_amdgcn_readlane((int)toff[j].y, tl);
+			const unsigned tw = (topa & 128) ? twh : twl;
+			ztop[j] = (int)((tw >> (16 * (topa & 1))) & 0xffffu) >> 3;
+			topaj[j] = topa;
+			tlj[j] = tl;
+		}
 #if NBL_EMS_PRUNE
 		if (tryf) {
 			// the best value beside rank 0: every lane's maximum, the lane that holds rank 0 with that slot left out; on float keys,
 			// rounded up by more than the rounding (an upper bound is all the pruning needs)
-			const int ts = (topa & 1) + 2 * (topa >> 7); // slot of rank 0 (wave-uniform)
-			// (selects, not v[j][ts]: a run-time index would put the vector into scratch memory)
-			const double mate = (ts == 0) ? v[j][1] : (ts == 1) ? v[j][0] : (ts == 2) ? v[j][3] : v[j][2]; // the other value of rank 0's 16-byte pair
-			const double far = (ts & 2) ? dmax(v[j][0], v[j][1]) : dmax(v[j][2], v[j][3]);                 // the other pair
-			const double loc2 = (lane == tl) ? dmax(mate, far) : loc;
-			const double sf = (double)unkey32(wave_max_i32(key32(loc2)));
-			sec[j] = uniform_f64((sf + __builtin_fabs(sf) * 0x1p-22) + 0x1p-120);
+			int k2[4];
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				const int ts = (topaj[j] & 1) + 2 * (topaj[j] >> 7); // slot of rank 0 (wave-uniform)
+				// (selects, not v[j][ts]: a run-time index would put the vector into scratch memory)
+				const double mate = (ts == 0) ? v[j][1] : (ts == 1) ? v[j][0] : (ts == 2) ? v[j][3] : v[j][2]; // the other value of rank 0's 16-byte pair
+				const double far = (ts & 2) ? dmax(v[j][0], v[j][1]) : dmax(v[j][2], v[j][3]);                 // the other pair
+				k2[j] = key32((lane == tlj[j]) ? dmax(mate, far) : loc[j]);
+			}
+			wave_reduce_i32x4<true>(k2);
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				const double sf = (double)unkey32(k2[j]);
+				sec[j] = uniform_f64((sf + __builtin_fabs(sf) * 0x1p-22) + 0x1p-120);
+			}
 		}
 #endif
 	}
@@ -536,9 +556,13 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 #if NBL_EMS_PRUNE
 	if (tryf) {
 		double flo[4]; // lower bounds of min_s S[x][s]
+		int kf[4];
+#pragma unroll
+		for (int x = 0; x < 4; x++) kf[x] = key32(dmin(dmin(S[x][0], S[x][1]), dmin(S[x][2], S[x][3])));
+		wave_reduce_i32x4<false>(kf);
 #pragma unroll
 		for (int x = 0; x < 4; x++) {
-			const double lf = (double)unkey32(wave_min_i32(key32(dmin(dmin(S[x][0], S[x][1]), dmin(S[x][2], S[x][3])))));
+			const double lf = (double)unkey32(kf[x]);
 			flo[x] = uniform_f64((lf - __builtin_fabs(lf) * 0x1p-22) - 0x1p-120);
 		}
 		auto pb = [&](int b, int c) { return dmax(mtop[b] + sec[c], sec[b] + mtop[c]); };
@@ -552,20 +576,31 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 		thr[2] = uniform_f64(dmin(dmin(low(flo[0], p13), low(flo[1], p03)), low(flo[3], p01)));
 		thr[3] = uniform_f64(dmin(dmin(low(flo[0], p12), low(flo[1], p02)), low(flo[2], p01)));
 		fast = true;
-#pragma unroll
-		for (int j = 0; j < 4; j++) {
-			int c = 0;
-#pragma unroll
-			for (int i = 0; i < 4; i++) c += __popcll(__ballot(!(v[j][i] < thr[j]))); // (the masks themselves are formed again at the compaction: 64 scalar registers otherwise)
-			cntl[j] = c;
-			fast = fast && c <= nmr;
-		}
 		// An edge with at most one entry at or above its threshold cannot deviate usefully: that entry is its rank 0.  nd = the edges
 		// that still can.  A configuration outside conf(q,1) deviates on two or more of an output's three other edges, so with nd <= 1
 		// none exists for any output: S[] is final, and everything between here and the emit stage is left out (bit-exact: a
 		// configuration with one deviation equals its conf(q,1) term, both sum the three other edges in index order).
-		nd = (cntl[0] >= 2) + (cntl[1] >= 2) + (cntl[2] >= 2) + (cntl[3] >= 2);
-		if (!fast) { cntl[0] = cntl[1] = cntl[2] = cntl[3] = nmr; nd = 4; }
+#if (NBL_EMS_TRIMS & 8) && NBL_EMS_ND
+		// sec[j] bounds every value of edge j beside rank 0 from above: sec[j] < thr[j] on all four edges proves at most one entry
+		// per edge at or above its threshold, nd = 0, from four compares of wave-uniform values -- the common class past convergence.
+		// (Exact: a looser sec only sends a check to the count below.  The lists are not built for nd = 0: cntl is not read.)
+		if ((sec[0] < thr[0]) & (sec[1] < thr[1]) & (sec[2] < thr[2]) & (sec[3] < thr[3])) {
+			cntl[0] = cntl[1] = cntl[2] = cntl[3] = 1;
+			nd = 0;
+		} else
+#endif
+		{
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				int c = 0;
+#pragma unroll
+				for (int i = 0; i < 4; i++) c += __popcll(__ballot(!(v[j][i] < thr[j]))); // (the masks themselves are formed again at the compaction: 64 scalar registers otherwise)
+				cntl[j] = c;
+				fast = fast && c <= nmr;
+			}
+			nd = (cntl[0] >= 2) + (cntl[1] >= 2) + (cntl[2] >= 2) + (cntl[3] >= 2);
+			if (!fast) { cntl[0] = cntl[1] = cntl[2] = cntl[3] = nmr; nd = 4; }
+		}
 #ifdef NBL_EMS_STAMPS
 		if (st_on) { st_acc[13] += fast ? 1 : 0; st_acc[14] += cntl[0] + cntl[1] + cntl[2] + cntl[3]; } // short-list checks, list entries
 		if (w.stamps) st_cls = fast ? nd : 5;
@@ -626,6 +661,19 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 			int *H = (int *)B0; // [4 edges][256 buckets] (spans B0 and B1); lane l reads buckets 4l .. 4l+3 of every edge
 			int one;            // the increment of the sixteen histogram atomics, held in ONE register (hipcc re-materialises a literal 1 per atomic)
 			asm volatile("v_mov_b32 %0, 1" : "=v"(one));
+#if NBL_EMS_TRIMS & 4
+			// the lower end of the bucket range is only needed here -- a check that ends on the short lists never forms it.  The lane
+			// maxima are taken again, over the check-domain registers: another arrangement of the same 256 values into 64 lanes, for
+			// which the bound holds as well (the keys of the rank-0 stage would be four registers live across conf(q,1))
+			{
+				int kmin[4];
+#pragma unroll
+				for (int j = 0; j < 4; j++) kmin[j] = key32(dmax(dmax(v[j][0], v[j][1]), dmax(v[j][2], v[j][3])));
+				wave_reduce_i32x4<false>(kmin);
+#pragma unroll
+				for (int j = 0; j < 4; j++) lmin[j] = lmin_of(kmin[j], mtop[j]);
+			}
+#endif
 			WSYNC();
 			{
 				int4 z4 = {0, 0, 0, 0};
@@ -815,11 +863,25 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 		// the list lives in the registers of lanes 0..NM-1 (one entry each); an entry reaches the whole wave through v_readlane
 		// (SGPR operands of the adds) -- the LDS port is the busier resource of this kernel, a broadcast read per entry costs more
 		const double myv = lstv[jc * NM + (lane & (NM - 1))];
-		const int mytt = lstt[jc * NM + (lane & (NM - 1))].y;
+		int mytt = lstt[jc * NM + (lane & (NM - 1))].y;
+#if NBL_EMS_TRIMS & 1
+		// tt = (t & 0x7E) << 3 has six significant bits (4..9): lane k packs the offsets of entries k .. k+3 into one word, entry k+u
+		// at bits 4+6u .. 9+6u (three wave shifts by one lane, once per gather), so a trip of four entries reads ONE word with
+		// v_readlane and takes its offsets apart on the scalar unit.  The window is indexed by the absolute list position k: it
+		// does not care where a run starts or ends; fields of entries beyond the list (the lanes wrap at NM) are never looked at.
+		{
+			auto next_lane = [](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x130, 0xF, 0xF, true); }; // wave_shl:1: lane l takes lane l+1 (lane 63: 0)
+			const int t1 = next_lane(mytt), t2 = next_lane(t1), t3 = next_lane(t2);
+			mytt |= (t1 << 6) | (t2 << 12) | (t3 << 18);
+		}
+#endif
 		auto entry = [&](int k) {
 			ListEnt e;
 			e.v = read_lane_f64(myv, k);
 			e.tt = __builtin_amdgcn_readlane(mytt, k);
+#if NBL_EMS_TRIMS & 1
+			e.tt &= 0x3F0;
+#endif
 			e.t8 = 0;
 			return e;
 		};
@@ -828,8 +890,19 @@ __global__ __launch_bounds__(64) void cn_ems_q256_dc4_kernel(NblGraphDev g, NblW
 			for (; k + UN <= k1; k += UN) {
 				STAMP_COUNT(11);
 				ListEnt en[UN];
+#if NBL_EMS_TRIMS & 1
+				static_assert(UN == 4, "one packed word holds the offsets of four entries");
+				const int w4 = __builtin_amdgcn_readlane(mytt, k);
+#pragma unroll
+				for (int u = 0; u < UN; u++) {
+					en[u].v = read_lane_f64(myv, k + u);
+					en[u].tt = (w4 >> (6 * u)) & 0x3F0;
+					en[u].t8 = 0;
+				}
+#else
 #pragma unroll
 				for (int u = 0; u < UN; u++) en[u] = entry(k + u);
+#endif
 #pragma unroll
 				for (int u = 0; u < UN; u++) body(en[u], swapped, upper);
 			}

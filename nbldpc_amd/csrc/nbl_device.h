@@ -122,6 +122,28 @@ __device__ __forceinline__ int wave_imax_id(int x)
 	return __builtin_amdgcn_readlane(x, 63);
 }
 
+// Four wave maxima (MAX) or minima of 32-bit integers at once.  One reduction is a chain of six dependent DPP instructions, and a
+// DPP instruction that reads the result of the one before it waits out a hazard (s_nop 1) on top of its latency; here step s of
+// all four keys is issued back to back -- four independent instructions -- before step s+1, so no step waits for its operand.
+// The same instructions and results as four single reductions (quad_perm, row mirrors, row broadcasts; lane 63 holds the result).
+template <bool MAX> __device__ __forceinline__ void wave_reduce_i32x4(int (&x)[4])
+{
+	constexpr int ID = MAX ? (int)0x80000000 : 0x7fffffff; // the identity as the DPP `old` value: hipcc folds the move into v_max_i32_dpp / v_min_i32_dpp
+	auto op = [](int a, int b) { return MAX ? (a > b ? a : b) : (a < b ? a : b); };
+	__builtin_amdgcn_sched_barrier(0); // all four keys first: the scheduler would otherwise start one chain alone while the other keys are formed
+#define NBL_RED4_STEP(CTRL, ROWS)                                                                                      \
+	_Pragma("unroll") for (int i = 0; i < 4; i++) x[i] = op(x[i], __builtin_amdgcn_update_dpp(ID, x[i], CTRL, ROWS, 0xF, false));
+	NBL_RED4_STEP(0xB1, 0xF)  // quad_perm [1,0,3,2]
+	NBL_RED4_STEP(0x4E, 0xF)  // quad_perm [2,3,0,1]
+	NBL_RED4_STEP(0x141, 0xF) // row_half_mirror
+	NBL_RED4_STEP(0x140, 0xF) // row_mirror
+	NBL_RED4_STEP(0x142, 0xA) // row_bcast15 into rows 1,3
+	NBL_RED4_STEP(0x143, 0xC) // row_bcast31 into rows 2,3
+#undef NBL_RED4_STEP
+#pragma unroll
+	for (int i = 0; i < 4; i++) x[i] = __builtin_amdgcn_readlane(x[i], 63);
+}
+
 __device__ __forceinline__ unsigned wave_umax_id(unsigned x)
 {
 	x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false));
