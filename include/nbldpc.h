@@ -89,7 +89,7 @@ typedef struct nbl_decoder nbl_decoder;
  * gf_inv[a] < q with gf_mul[a][gf_inv[a]] == 1 (which no reducible m can meet).  Anything else is NBL_ERR_ARG, the message
  * names the first offending entry.
  * Shapes: q = 4 .. 256 (a power of two), check and variable degrees up to 8, ems_nm <= q, T-EMS with p * (largest check
- * degree) <= 32 (q = 2^p; the path code of TEMS_ConstructConf in 32 bits); anything else is NBL_ERR_UNSUPPORTED / NBL_ERR_ARG
+ * degree) <= 32 (q = 2^p; the path code of TEMS_ConstructConf in 32 bits; nbl_create_tems_wide has neither limit); anything else is NBL_ERR_UNSUPPORTED / NBL_ERR_ARG
  * with a message, at creation, never at the first decode. */
 nbl_status nbl_create(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv,
                       const nbl_params *params, int device, nbl_decoder **out);
@@ -312,11 +312,38 @@ nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, con
  *   point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the
  *   active list, the transmitter, channel and error count work unchanged on such a decoder.  nbl_read_state returns post and c2v as on the
  *   corresponding EMS decoder (a non-NULL v2c is refused on the layered kind, as there); nbl_get_layers works on the layered kind.
- *   Every other entry point but nbl_create_fht keeps its check-degree limit of 8. */
+ *   Every other entry point but nbl_create_fht and nbl_create_tems_wide keeps its check-degree limit of 8. */
 #define NBL_EMS_MAX_CHECK_DEGREE 32
 #define NBL_EMS_WIDE_LAYERED 1u
 nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
+/* ---- T-EMS decoding for high-rate codes: check degrees up to 32 over any field, flooding and layered ----------------------------------
+ * nbl_create_tems_wide: NBL_METHOD_TEMS only (no OSD, no extension parameters).  There is no new arithmetic: dW and Eta of a check are
+ * the smallest (cost, path in enumeration order) over the paths with at most tems_nc deviations inside the tems_nr marks, costs as
+ * left-to-right sums -- the T-EMS check node defined above, which is generic in the check degree; out_sym, converged, iters, post, c2v
+ * and v2c equal the canonical oracle's bit for bit at every degree.  What nbl_create cannot hold above log2(q) * (check degree) = 32 is
+ * the path of a check sum as base-q digits in one 32-bit word; here a path is stored as its at most NBL_TEMS_WIDE_MAX_NC = 4 deviations
+ * (column, symbol) in one 64-bit word that orders like the digit string.
+ *   flags 0: word for word the flooding T-EMS decoder of nbl_create (a non-NULL layer_of is NBL_ERR_ARG).  NBL_TEMS_WIDE_LAYERED: word for
+ *   word the damped layered schedule of nbl_create_layered_ex(.., NBL_LAYERED_DAMPED) -- the same layer rules and refusal texts,
+ *   nbl_layer_greedy for layer_of == NULL.  An unknown flag bit is NBL_ERR_ARG.
+ *   Limits: check degrees 2 .. 32 (NBL_TEMS_MAX_CHECK_DEGREE; a larger check is NBL_ERR_ARG, the message names this entry point, the degree
+ *   found and 32); variable degrees stay 1 .. 8, with nbl_create's text; nbl_create's limit log2(q) * (largest check degree) <= 32 does not
+ *   apply.  Any other method is NBL_ERR_UNSUPPORTED (the message names method 4).  On a code with a check above degree 8 or with
+ *   log2(q) * (largest check degree) > 32, tems_nc above 4 is NBL_ERR_UNSUPPORTED (the message names both numbers), and a check is run by
+ *   one workgroup whose LDS holds [maxdc][q] dU, the DP states [2][nc + 1][q] of 16 bytes, at most min(nr, maxdc) (q - 1) list entries of
+ *   16 bytes and two [q] vectors; a shape that needs more than 160 KB is NBL_ERR_UNSUPPORTED and the message names the byte count.
+ *   Everything else nbl_create refuses is refused the same way; all of it before the device is touched.
+ *   Any other code gets exactly the decoder nbl_create / nbl_create_layered_ex would make.  Every decode entry point (host, device, bits,
+ *   samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the active list, the transmitter,
+ *   channel and error count work unchanged on such a decoder.  nbl_read_state returns post, c2v and v2c as on the corresponding T-EMS
+ *   decoder; nbl_get_layers works on the layered kind.
+ *   Every other entry point but nbl_create_fht and nbl_create_ems_wide keeps its check-degree limit of 8. */
+#define NBL_TEMS_MAX_CHECK_DEGREE 32
+#define NBL_TEMS_WIDE_LAYERED 1u
+nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "nbl_decoder.h"
+#include "nbl_tems_path.h" // NBL_TEMS_WIDE_MAX_NC
 
 template <typename T> static nbl_status upload(nbl_decoder *d, const std::vector<T> &h, const T **dst)
 {
@@ -246,7 +247,7 @@ struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out,
-                              bool fht = false, bool ems_wide = false);
+                              bool fht = false, bool ems_wide = false, bool tems_wide = false);
 
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
@@ -307,6 +308,22 @@ extern "C" nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint1
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_EMS_WIDE_LAYERED) ? &lay : nullptr, device, out, false, true);
 }
 
+// T-EMS with check degrees up to NBL_TEMS_MAX_CHECK_DEGREE over any field (include/nbldpc.h): flooding without a LayerReq, layered with the
+// request of nbl_create_layered_ex(.., NBL_LAYERED_DAMPED) -- the same assignment rules, the same v2c state
+extern "C" nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                           const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	if (!out) return NBL_ERR_ARG;
+	*out = nullptr;
+	if (flags & ~(uint32_t)NBL_TEMS_WIDE_LAYERED)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_TEMS_WIDE_LAYERED = 1 is the only one defined)");
+	if (!(flags & NBL_TEMS_WIDE_LAYERED) && layer_of)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or "
+		                                         "set NBL_TEMS_WIDE_LAYERED)");
+	const LayerReq lay = {layer_of, NBL_LAYERED_DAMPED, false};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_TEMS_WIDE_LAYERED) ? &lay : nullptr, device, out, false, false, true);
+}
+
 extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
 {
 	if (!d || !d->layered) return NBL_ERR_ARG;
@@ -316,7 +333,8 @@ extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, in
 }
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
-                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht, bool ems_wide)
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht, bool ems_wide,
+                              bool tems_wide)
 {
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
@@ -336,6 +354,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (ems_wide && params->method != NBL_METHOD_EMS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide runs EMS (method 2) only: the other methods keep their entry points and their check-degree "
 		                                                 "limit of 8 (log-QSPA above it: nbl_create_fht)");
+	if (tems_wide && params->method != NBL_METHOD_TEMS)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide runs T-EMS (method 4) only: the other methods keep their entry points (EMS above check "
+		                                                 "degree 8: nbl_create_ems_wide, log-QSPA: nbl_create_fht)");
 	if (lay && lay->bp && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_layered_bp runs log-QSPA (method 1) only: the layered schedule of EMS (method 2) is behind "
 		                                                 "nbl_create_layered, that of T-EMS (method 4) behind nbl_create_layered_ex with NBL_LAYERED_DAMPED");
@@ -434,7 +455,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (ems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_EMS_MAX_CHECK_DEGREE)
 		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
 		                                         std::to_string(NBL_EMS_MAX_CHECK_DEGREE) + ")");
-	if ((!fht && !ems_wide && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
+	// (nbl_create_tems_wide: the same shape of programme; its path code holds columns up to 31)
+	if (tems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_TEMS_MAX_CHECK_DEGREE)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
+		                                         std::to_string(NBL_TEMS_MAX_CHECK_DEGREE) + ")");
+	if ((!fht && !ems_wide && !tems_wide && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
 	static_assert(NBL_LAYER_ROW >= 4 + NBL_MAXDV, "a layer row holds the c2v slots of every edge of a variable");
 	std::vector<int> v_cpos(E, -1), c_epos(E, -1), c_var(E), c_h(E), c_hinv(E);
 	for (int ce = 0; ce < E; ce++) {
@@ -460,7 +485,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 			if (c_epos[ce] < 0) return fail_create(nullptr, NBL_ERR_ARG, "check-side edge without variable-side partner");
 		}
 	// shape limits of the kernels, refused here rather than at the first decode
-	if (params->method == NBL_METHOD_TEMS && p * maxdc > 32)
+	// (nbl_create_tems_wide: such a code runs the programme whose path code does not grow with the degree, nbl_tems_path.h)
+	const bool tems_needs_wide = tems_wide && nbl_tems_needs_wide(shape);
+	if (params->method == NBL_METHOD_TEMS && !tems_wide && p * maxdc > 32)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: log2(q) * (largest check degree) must not exceed 32 (the trellis path code is one 32-bit word)");
 	// (a wide decoder with maxdc <= NBL_MAXDC may run either programme: both bounds hold, the general kernel's first, with nbl_create's text)
 	if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024)
@@ -468,6 +495,14 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (ems_wide && nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > NBL_EMS_WIDE_MAX_LDS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide: this (q, check degree, nm, nc) needs " +
 		                                                 std::to_string(nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc)) +
+		                                                 " bytes of LDS per check, more than the 160 KB (163840 bytes) one workgroup can have");
+	if (tems_needs_wide && params->tems_nc > NBL_TEMS_WIDE_MAX_NC)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide: tems_nc = " + std::to_string(params->tems_nc) + " above " + std::to_string(NBL_TEMS_WIDE_MAX_NC) +
+		                                                 " (NBL_TEMS_WIDE_MAX_NC: the deviations one 64-bit path code holds) on a code whose checks need the wide programme");
+	// (inside nbl_create's envelope the bound holds wherever switch 3 may select the wide programme; it is far from it there)
+	if (tems_wide && params->tems_nc <= NBL_TEMS_WIDE_MAX_NC && nbl_tems_wide_lds_bytes(q, maxdc, params->tems_nr, params->tems_nc) > NBL_TEMS_WIDE_MAX_LDS)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide: this (q, check degree, nr, nc) needs " +
+		                                                 std::to_string(nbl_tems_wide_lds_bytes(q, maxdc, params->tems_nr, params->tems_nc)) +
 		                                                 " bytes of LDS per check, more than the 160 KB (163840 bytes) one workgroup can have");
 	// ---- layered schedule: the assignment, checked or made here, before the device is touched ----
 	std::vector<int> layer_of, lay_off, lay_chk, lay_nbr;
@@ -477,7 +512,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		// (log-QSPA: (3 maxdc + 5) q 8 bytes, at most 59,392 B at q = 256 and degree 8 -- nothing to refuse; FHT: maxdc q 8 bytes, at most
 		// 65,536 B at q = 256 and degree 32, what a launch gets without opting in -- nothing to refuse either)
 		if (params->method == NBL_METHOD_TEMS) {
-			if (nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
+			if (!tems_needs_wide && nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");
 		} else if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
 			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
@@ -546,6 +581,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	}
 	d->fht = fht;
 	d->ems_wide = ems_wide;
+	d->tems_wide = tems_wide;
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;

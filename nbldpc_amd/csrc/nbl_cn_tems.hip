@@ -9,22 +9,6 @@
 #include "nbl_cn_tems_core.h"
 #include <cstdlib>
 
-// entry lane + 64 i of edge d's v2c vector (symbol 0 is taken as 0.0)
-template <int Q> struct TemsV2cInput {
-	const double *V; // the codeword's v2c block
-	const int *epos; // c_epos + c0
-	int lane;
-	__device__ __forceinline__ void operator()(int d, double (&v)[Fld<Q>::NS]) const
-	{
-		const double *Vd = V + (size_t)epos[d] * Q;
-#pragma unroll
-		for (int i = 0; i < Fld<Q>::NS; i++) {
-			int a = lane + 64 * i;
-			v[i] = (a < Q && a > 0) ? Vd[a] : 0.0;
-		}
-	}
-};
-
 template <int Q>
 __global__ __launch_bounds__(64) void cn_tems_kernel(NblGraphDev g, NblWork w, NblRun r)
 {

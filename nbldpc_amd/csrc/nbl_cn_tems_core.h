@@ -30,6 +30,23 @@
 #include <hip/hip_runtime.h>
 #include "nbl_device.h"
 
+// the flooding schedule's input (nbl_cn_tems.hip, nbl_cn_tems_wide.hip): entry lane + 64 i of edge d's v2c vector, as the variable-node
+// pass wrote it (symbol 0 is taken as 0.0)
+template <int Q> struct TemsV2cInput {
+	const double *V; // the codeword's v2c block
+	const int *epos; // c_epos + c0
+	int lane;
+	__device__ __forceinline__ void operator()(int d, double (&v)[Fld<Q>::NS]) const
+	{
+		const double *Vd = V + (size_t)epos[d] * Q;
+#pragma unroll
+		for (int i = 0; i < Fld<Q>::NS; i++) {
+			int a = lane + 64 * i;
+			v[i] = (a < Q && a > 0) ? Vd[a] : 0.0;
+		}
+	}
+};
+
 // ---- 1. beta, syndrome, dU: returns the syndrome -----------------------------------------------------------------------------
 template <int Q, class Input>
 __device__ __forceinline__ int tems_stage_inputs(const NblGraphDev &g, int c0, int dc, int lane, double *dU, int *beta, Input input)

@@ -54,6 +54,15 @@ size_t nbl_ems_wide_lds_bytes(int q, int maxdc, int nm, int nc);
 hipError_t nbl_launch_cn_ems_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_ems_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// T-EMS check node for checks up to degree NBL_TEMS_MAX_CHECK_DEGREE over any field (nbl_create_tems_wide; nbl_cn_tems_wide.hip): the
+// programme of nbl_cn_tems_wide_core.h, one check per workgroup of max(1, q / 64) waves, at most NBL_TEMS_WIDE_MAX_NC (nbl_tems_path.h)
+// deviations per path, flooding and the checks of one layer.  The bytes of LDS of one workgroup are pure arithmetic:
+// nbl_create_tems_wide refuses above NBL_TEMS_WIDE_MAX_LDS before the device, both launchers size by it
+#define NBL_TEMS_WIDE_MAX_LDS (160 * 1024)
+size_t nbl_tems_wide_lds_bytes(int q, int maxdc, int nr, int nc);
+hipError_t nbl_launch_cn_tems_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_tems_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 size_t nbl_ems256_lds_bytes(int nm);
 hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);

@@ -13,6 +13,7 @@ enum NblCn {
 	NBL_CN_FHT, NBL_CN_FHT_LAYERED, // nbl_create_fht: the FHT sum-product check node, flooding and layered
 	NBL_CN_FHT_WIDE, NBL_CN_FHT_WIDE_LAYERED, // the same in the degree-independent layout: codes with a check above degree NBL_MAXDC
 	NBL_CN_EMS_WIDE, NBL_CN_EMS_WIDE_LAYERED, // nbl_create_ems_wide: EMS, one check per workgroup, any check degree up to NBL_EMS_MAX_CHECK_DEGREE
+	NBL_CN_TEMS_WIDE, NBL_CN_TEMS_WIDE_LAYERED, // nbl_create_tems_wide: T-EMS, one check per workgroup, 64-bit path code, check degrees up to NBL_TEMS_MAX_CHECK_DEGREE
 	NBL_CN_COUNT
 };
 
@@ -29,9 +30,14 @@ NblShape nbl_shape(const nbl_code_desc *code);
 // fht: an nbl_create_fht decoder (method 1; `layered` says which of its two schedules); there force_generic 3 selects the wide
 // programme at any check degree (so that the two layouts can be compared on the same inputs) and 0, 1, 2 change nothing;
 // ems_wide: an nbl_create_ems_wide decoder (method 2): a code with a check above degree NBL_MAXDC runs ems_wide / ems_wide_layered under
-// every switch; any other code gets the plan of nbl_create / nbl_create_layered, except that force_generic 3 selects the wide programme
+// every switch; any other code gets the plan of nbl_create / nbl_create_layered, except that force_generic 3 selects the wide programme;
+// tems_wide: an nbl_create_tems_wide decoder (method 4): a code with a check above degree NBL_MAXDC or with log2(q) maxdc > 32 (the path
+// does not fit tems_check_node's 32-bit code) runs tems_wide / tems_wide_layered under every switch; any other code gets the plan of
+// nbl_create / nbl_create_layered_ex, except that force_generic 3 selects the wide programme where tems_nc <= NBL_TEMS_WIDE_MAX_NC
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht = false, bool ems_wide = false);
+                 bool small_on, bool fht = false, bool ems_wide = false, bool tems_wide = false);
+// the codes only the wide T-EMS programme runs (creation refuses tems_nc > NBL_TEMS_WIDE_MAX_NC there)
+inline bool nbl_tems_needs_wide(const NblShape &s) { return s.maxdc > NBL_MAXDC || s.p * s.maxdc > 32; }
 const char *nbl_cn_name(NblCn cn);
 
 // What each specialised kernel can run, beside the kernel (its LDS arithmetic lives there); nbl_plan is the only caller.

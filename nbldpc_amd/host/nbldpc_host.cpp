@@ -143,7 +143,23 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = wide      ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)
+	// NBL_TEMS_WIDE=1: T-EMS through nbl_create_tems_wide, which takes check degrees up to NBL_TEMS_MAX_CHECK_DEGREE over any field (off by
+	// default, NBL_TEMS_WIDE=0 names the default).  A T-EMS profile (method 4) without OSD only; combines with NBL_SCHEDULE=flooding (or
+	// unset) and layered-damped
+	const char *twenv = getenv("NBL_TEMS_WIDE");
+	const bool twide = twenv && std::string(twenv) == "1";
+	if (twenv && !twide && std::string(twenv) != "0") {
+		error = std::string("NBL_TEMS_WIDE=") + twenv + ": unknown value (0, 1)";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (twide && (sim.decodeMethod != T_EMS_DECODE || osd || wide || fht || (layered && !damped))) {
+		error = "NBL_TEMS_WIDE=1: the wide T-EMS decoder is defined for T-EMS (method 4) without OSD only, under NBL_SCHEDULE=flooding or layered-damped";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	nbl_status st = twide     ? nbl_create_tems_wide(&code, mul.data(), inv.data(), &p, nullptr, damped ? NBL_TEMS_WIDE_LAYERED : 0u, device, &dec)
+	                : wide    ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)
 	                : fht     ? nbl_create_fht(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT_LAYERED : 0u, device, &dec)
 	                : lay_bp  ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
 	                : damped  ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
