@@ -312,7 +312,7 @@ nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, con
  *   point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the
  *   active list, the transmitter, channel and error count work unchanged on such a decoder.  nbl_read_state returns post and c2v as on the
  *   corresponding EMS decoder (a non-NULL v2c is refused on the layered kind, as there); nbl_get_layers works on the layered kind.
- *   Every other entry point but nbl_create_fht and nbl_create_tems_wide keeps its check-degree limit of 8. */
+ *   Every other entry point but nbl_create_fht, nbl_create_tems_wide and nbl_create_bp_wide keeps its check-degree limit of 8. */
 #define NBL_EMS_MAX_CHECK_DEGREE 32
 #define NBL_EMS_WIDE_LAYERED 1u
 nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
@@ -339,11 +339,36 @@ nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul
  *   samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the active list, the transmitter,
  *   channel and error count work unchanged on such a decoder.  nbl_read_state returns post, c2v and v2c as on the corresponding T-EMS
  *   decoder; nbl_get_layers works on the layered kind.
- *   Every other entry point but nbl_create_fht and nbl_create_ems_wide keeps its check-degree limit of 8. */
+ *   Every other entry point but nbl_create_fht, nbl_create_ems_wide and nbl_create_bp_wide keeps its check-degree limit of 8. */
 #define NBL_TEMS_MAX_CHECK_DEGREE 32
 #define NBL_TEMS_WIDE_LAYERED 1u
 nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                 const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
+/* ---- Exact log-QSPA for high-rate codes: check degrees up to 32, flooding and layered --------------------------------------------------
+ * nbl_create_bp_wide: NBL_METHOD_BP only (no OSD, no extension parameters).  There is no new arithmetic: a check's output is the
+ * log-QSPA update (forward and backward partials, XOR convolutions in the log-sum-exp semiring) as every log-QSPA kernel of this library
+ * evaluates it, which is generic in the check degree.  Parity is the method's own: hard decisions, converged flags and iteration counts
+ * equal those of the FP64 restatement on inputs whose decisions have a margin; post, c2v and v2c agree with it within 1e-9 of the largest
+ * magnitude.  (FHT decoding, nbl_create_fht, is a decoder kind of its own with a floor; this is the exact method it is measured against.)
+ *   flags 0: word for word the flooding log-QSPA decoder of nbl_create (a non-NULL layer_of is NBL_ERR_ARG).  NBL_BP_WIDE_LAYERED: word for
+ *   word the schedule of nbl_create_layered_bp -- the same layer rules and refusal texts, nbl_layer_greedy for layer_of == NULL.  An
+ *   unknown flag bit is NBL_ERR_ARG.
+ *   Limits: check degrees 2 .. 32 (NBL_BP_MAX_CHECK_DEGREE; a larger check is NBL_ERR_ARG, the message names this entry point, the degree
+ *   found and 32); variable degrees stay 1 .. 8, with nbl_create's text.  Any other method is NBL_ERR_UNSUPPORTED (the message names
+ *   method 1).  A check above degree 8 is run by one workgroup of max(1, q / 64) waves whose LDS holds the [maxdc][q] inputs, one [q]
+ *   vector and two [q] blocks of 16 bytes: (maxdc + 5) q 8 + 256 bytes, at most 76,032 at q = 256 and degree 32, so no shape is refused
+ *   for its LDS.  Everything else nbl_create refuses is refused the same way; all of it before the device is touched.
+ *   A code whose checks all have degree 8 or less gets exactly the decoder nbl_create / nbl_create_layered_bp would make, the fused
+ *   kernels included; on such a code the two layouts evaluate the same operations in the same order and give the same bits.  Every decode
+ *   entry point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and
+ *   the active list, the transmitter, channel and error count work unchanged on such a decoder.  nbl_read_state returns post, c2v and v2c
+ *   as on the corresponding log-QSPA decoder; nbl_get_layers works on the layered kind.
+ *   Every other entry point but nbl_create_fht, nbl_create_ems_wide and nbl_create_tems_wide keeps its check-degree limit of 8. */
+#define NBL_BP_MAX_CHECK_DEGREE 32
+#define NBL_BP_WIDE_LAYERED 1u
+nbl_status nbl_create_bp_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                              const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the

@@ -20,10 +20,11 @@ SOFT_EXTRINSIC = 1
 FHT_LAYERED = 1          # NBL_FHT_LAYERED
 EMS_WIDE_LAYERED = 1     # NBL_EMS_WIDE_LAYERED
 TEMS_WIDE_LAYERED = 1    # NBL_TEMS_WIDE_LAYERED
+BP_WIDE_LAYERED = 1      # NBL_BP_WIDE_LAYERED
 FADING_NONE, FADING_RAYLEIGH = 0, 1
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_create_layered_bp", "nbl_create_fht", "nbl_create_ems_wide", "nbl_create_tems_wide", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_create_layered_bp", "nbl_create_fht", "nbl_create_ems_wide", "nbl_create_tems_wide", "nbl_create_bp_wide", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
@@ -109,6 +110,8 @@ def load_library():
         L.nbl_create_ems_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_create_tems_wide.restype = C.c_int
         L.nbl_create_tems_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_create_bp_wide.restype = C.c_int
+        L.nbl_create_bp_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_get_layers.restype = C.c_int
         L.nbl_get_layers.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.nbl_destroy.argtypes = [C.c_void_p]
@@ -197,18 +200,28 @@ class PlanInfo(C.Structure):
 
 
 def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=None, bs_nc=2, layers=None, damped=None,
-               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False):
+               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False):
     """The check-node kernel a decoder of this description would run (nbl_debug_plan; host arithmetic, no device, no decoder):
     (kernel name, fusable, fused, want_v2c).  The description is built the way Decoder builds it; layers / damped / fht as there
     (None = flooding), force_generic as nbl_debug_force_generic takes it (with fht, 3 names the wide programme, fht_wide /
     fht_wide_layered, at any check degree; with wide, the decoder nbl_create_ems_wide would make: 3 names ems_wide / ems_wide_layered at
     any check degree; with tems_wide, the decoder nbl_create_tems_wide would make: 3 names tems_wide / tems_wide_layered at any check
-    degree where tems_nc <= 4), record_state as nbl_set_record_state."""
+    degree where tems_nc <= 4; with bp_wide, the decoder nbl_create_bp_wide would make: 3 names bp_wide / bp_wide_layered at any check
+    degree), record_state as nbl_set_record_state.  fht, wide, tems_wide and bp_wide exclude one another."""
+    if sum(map(bool, (fht, wide, tems_wide, bp_wide))) > 1:
+        raise ValueError("fht, wide, tems_wide and bp_wide name four different entry points: give one of them")
     lib = load_library()
     params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
     ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
     desc = code.desc()
     out = PlanInfo()
+    if bp_wide:
+        lib.nbl_debug_plan_bp_wide.restype = C.c_int
+        lib.nbl_debug_plan_bp_wide.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
+        rc = lib.nbl_debug_plan_bp_wide(C.byref(desc), C.byref(params), 0 if layers is None else BP_WIDE_LAYERED, force_generic, int(record_state), C.byref(out))
+        if rc != 0:
+            raise NblError(rc, "nbl_debug_plan_bp_wide")
+        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
     if tems_wide:
         lib.nbl_debug_plan_tems_wide.restype = C.c_int
         lib.nbl_debug_plan_tems_wide.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
@@ -256,12 +269,14 @@ class Decoder:
     nbl_create_layered (layers="greedy" or an assignment) with check degrees up to NBL_EMS_MAX_CHECK_DEGREE = 32.  tems_wide=True (method 4
     only; without wide, damped, bp, fht, OSD or extension parameters): nbl_create_tems_wide, the T-EMS decoder of nbl_create (without
     layers) or of nbl_create_layered_ex with NBL_LAYERED_DAMPED (layers="greedy" or an assignment) with check degrees up to
-    NBL_TEMS_MAX_CHECK_DEGREE = 32 over any field and tems_nc up to 4 there."""
+    NBL_TEMS_MAX_CHECK_DEGREE = 32 over any field and tems_nc up to 4 there.  bp_wide=True (method 1 only; without fht, wide, tems_wide,
+    damped, bp, OSD or extension parameters): nbl_create_bp_wide, the exact log-QSPA decoder of nbl_create (without layers) or of
+    nbl_create_layered_bp (layers="greedy" or an assignment) with check degrees up to NBL_BP_MAX_CHECK_DEGREE = 32."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False):
+                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -284,6 +299,11 @@ class Decoder:
         if tems_wide and (wide or fht or bp or damped is not None or osd_order is not None or bs_nm is not None):
             raise ValueError("tems_wide: nbl_create_tems_wide takes no wide / damped / bp / fht flag and neither OSD nor extension parameters (layers alone picks its "
                              "schedule; the layered one is the damped one)")
+        if bp_wide and (fht or wide or tems_wide):
+            raise ValueError("bp_wide: fht, wide and tems_wide name other entry points (nbl_create_fht, nbl_create_ems_wide, nbl_create_tems_wide): give one of them")
+        if bp_wide and (bp or damped is not None or osd_order is not None or bs_nm is not None):
+            raise ValueError("bp_wide: nbl_create_bp_wide takes no damped / bp flag and neither OSD nor extension parameters (layers alone picks its schedule; "
+                             "the layered one is that of nbl_create_layered_bp)")
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
                 raise ValueError("layers: nbl_create_layered takes neither OSD nor extension parameters")
@@ -291,7 +311,9 @@ class Decoder:
             if self._layer_of is not None and self._layer_of.shape != (code.M,):
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
             lay = None if self._layer_of is None else self._layer_of.ctypes.data
-            if tems_wide:
+            if bp_wide:
+                rc = self.lib.nbl_create_bp_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, BP_WIDE_LAYERED, device, C.byref(h))
+            elif tems_wide:
                 rc = self.lib.nbl_create_tems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, TEMS_WIDE_LAYERED, device, C.byref(h))
             elif wide:
                 rc = self.lib.nbl_create_ems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, EMS_WIDE_LAYERED, device, C.byref(h))
@@ -304,6 +326,8 @@ class Decoder:
             else:
                 rc = self.lib.nbl_create_layered_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,
                                                     int(damped), device, C.byref(h))
+        elif bp_wide:
+            rc = self.lib.nbl_create_bp_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
         elif tems_wide:
             rc = self.lib.nbl_create_tems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
         elif wide:

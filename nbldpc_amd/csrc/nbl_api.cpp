@@ -39,7 +39,7 @@ static bool small_enabled()
 // The kernel choice of this decoder as it stands (nbl_plan.cpp): once per workspace check and once per decode, never per launch
 static NblPlan plan_of(const nbl_decoder *d)
 {
-	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled(), d->fht, d->ems_wide, d->tems_wide);
+	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled(), d->fht, d->ems_wide, d->tems_wide, d->bp_wide);
 }
 
 nbl_status ensure_workspace(nbl_decoder *d, int B)
@@ -125,7 +125,7 @@ extern "C" nbl_status nbl_set_profiling(nbl_decoder *d, int32_t on)
 // Diagnostic only (not part of include/nbldpc.h): route every shape through the generic kernels (1), the specialised ones without the
 // fused iteration (2); on an nbl_create_fht decoder 3 selects the wide programme (nbl_cn_fht_wide.hip) at any check degree, on an
 // nbl_create_ems_wide decoder the workgroup-per-check programme (nbl_cn_ems_wide.hip), on an nbl_create_tems_wide decoder with
-// tems_nc <= NBL_TEMS_WIDE_MAX_NC that of nbl_cn_tems_wide.hip.
+// tems_nc <= NBL_TEMS_WIDE_MAX_NC that of nbl_cn_tems_wide.hip, on an nbl_create_bp_wide decoder that of nbl_cn_bp_wide.hip.
 extern "C" nbl_status nbl_debug_force_generic(nbl_decoder *d, int32_t on)
 {
 	if (!d) return NBL_ERR_ARG;
@@ -242,6 +242,20 @@ extern "C" nbl_status nbl_debug_plan_tems_wide(const nbl_code_desc *code, const 
 // creation's refusal and both launchers use
 extern "C" uint64_t nbl_debug_tems_wide_lds_bytes(int32_t q, int32_t maxdc, int32_t nr, int32_t nc) { return nbl_tems_wide_lds_bytes(q, maxdc, nr, nc); }
 
+// The same for a decoder nbl_create_bp_wide would make; wide_flags: NBL_BP_WIDE_* of include/nbldpc.h
+extern "C" nbl_status nbl_debug_plan_bp_wide(const nbl_code_desc *code, const nbl_params *params, uint32_t wide_flags, int32_t force_generic, int32_t record_state,
+                                             nbl_plan_info *out)
+{
+	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
+	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (wide_flags & NBL_BP_WIDE_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), false, false, false, true);
+	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
+	return NBL_OK;
+}
+
+// Diagnostic only (not part of include/nbldpc.h): the bytes of LDS one check of the wide log-QSPA programme takes -- the one function both
+// launchers size by (below 160 KB for every shape the ABI accepts: creation has nothing to refuse)
+extern "C" uint64_t nbl_debug_bp_wide_lds_bytes(int32_t q, int32_t maxdc) { return nbl_bp_wide_lds_bytes(q, maxdc); }
+
 // Diagnostic only (not part of include/nbldpc.h): the path code (nbl_tems_path.h) of the path that deviates to syms[i] in column cols[i],
 // i < n <= NBL_TEMS_WIDE_MAX_NC, columns ascending -- built by the kernels' own append, one deviation after the other; 0 for arguments
 // outside that
@@ -281,6 +295,7 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_FHT_WIDE: HIP_TRY(d, nbl_launch_cn_fht_wide(g, w, r, st)); break;
 	case NBL_CN_EMS_WIDE: HIP_TRY(d, nbl_launch_cn_ems_wide(g, w, r, st)); break;
 	case NBL_CN_TEMS_WIDE: HIP_TRY(d, nbl_launch_cn_tems_wide(g, w, r, st)); break;
+	case NBL_CN_BP_WIDE: HIP_TRY(d, nbl_launch_cn_bp_wide(g, w, r, st)); break;
 	case NBL_CN_BSTEMS: HIP_TRY(d, nbl_launch_cn_bstems(g, w, r, st)); break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
@@ -347,6 +362,7 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 				case NBL_CN_FHT_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_EMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_TEMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				case NBL_CN_BP_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_FHT_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				default: d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED;
 				}

@@ -247,7 +247,7 @@ struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out,
-                              bool fht = false, bool ems_wide = false, bool tems_wide = false);
+                              bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false);
 
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
@@ -324,6 +324,22 @@ extern "C" nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_TEMS_WIDE_LAYERED) ? &lay : nullptr, device, out, false, false, true);
 }
 
+// Exact log-QSPA with check degrees up to NBL_BP_MAX_CHECK_DEGREE (include/nbldpc.h): flooding without a LayerReq, layered with the request
+// of nbl_create_layered_bp -- the same assignment rules, the same v2c state
+extern "C" nbl_status nbl_create_bp_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                         const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	if (!out) return NBL_ERR_ARG;
+	*out = nullptr;
+	if (flags & ~(uint32_t)NBL_BP_WIDE_LAYERED)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_bp_wide: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_BP_WIDE_LAYERED = 1 is the only one defined)");
+	if (!(flags & NBL_BP_WIDE_LAYERED) && layer_of)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_bp_wide: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or "
+		                                         "set NBL_BP_WIDE_LAYERED)");
+	const LayerReq lay = {layer_of, 0, true};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_BP_WIDE_LAYERED) ? &lay : nullptr, device, out, false, false, false, true);
+}
+
 extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
 {
 	if (!d || !d->layered) return NBL_ERR_ARG;
@@ -334,7 +350,7 @@ extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, in
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht, bool ems_wide,
-                              bool tems_wide)
+                              bool tems_wide, bool bp_wide)
 {
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
@@ -357,6 +373,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (tems_wide && params->method != NBL_METHOD_TEMS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide runs T-EMS (method 4) only: the other methods keep their entry points (EMS above check "
 		                                                 "degree 8: nbl_create_ems_wide, log-QSPA: nbl_create_fht)");
+	if (bp_wide && params->method != NBL_METHOD_BP)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_bp_wide runs exact log-QSPA (method 1) only: the other methods keep their entry points (EMS above check "
+		                                                 "degree 8: nbl_create_ems_wide, T-EMS: nbl_create_tems_wide)");
 	if (lay && lay->bp && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_layered_bp runs log-QSPA (method 1) only: the layered schedule of EMS (method 2) is behind "
 		                                                 "nbl_create_layered, that of T-EMS (method 4) behind nbl_create_layered_ex with NBL_LAYERED_DAMPED");
@@ -459,7 +478,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (tems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_TEMS_MAX_CHECK_DEGREE)
 		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
 		                                         std::to_string(NBL_TEMS_MAX_CHECK_DEGREE) + ")");
-	if ((!fht && !ems_wide && !tems_wide && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
+	// (nbl_create_bp_wide: the same shape of programme; (maxdc + 5) q 8 + 256 bytes of LDS, at most 76,032 B -- nothing to refuse for LDS)
+	if (bp_wide && maxdv <= NBL_MAXDV && maxdc > NBL_BP_MAX_CHECK_DEGREE)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_bp_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
+		                                         std::to_string(NBL_BP_MAX_CHECK_DEGREE) + ")");
+	if ((!fht && !ems_wide && !tems_wide && !bp_wide && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
 	static_assert(NBL_LAYER_ROW >= 4 + NBL_MAXDV, "a layer row holds the c2v slots of every edge of a variable");
 	std::vector<int> v_cpos(E, -1), c_epos(E, -1), c_var(E), c_h(E), c_hinv(E);
 	for (int ce = 0; ce < E; ce++) {
@@ -509,7 +532,10 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	int n_layers = 0;
 	if (lay) {
 		// (the layered kernel is the general one: no specialised shape stands in for it, so the LDS bound holds for every shape)
-		// (log-QSPA: (3 maxdc + 5) q 8 bytes, at most 59,392 B at q = 256 and degree 8 -- nothing to refuse; FHT: maxdc q 8 bytes, at most
+		// (log-QSPA: (3 maxdc + 5) q 8 bytes, at most 59,392 B at q = 256 and degree 8, the largest check every entry point but
+		// nbl_create_bp_wide accepts -- nothing to refuse; above degree 8 nbl_create_bp_wide runs the workgroup-per-check programme alone,
+		// (maxdc + 5) q 8 + 256 bytes, at most 76,032 B at q = 256 and degree 32 (nbl_bp_wide_lds_bytes), which its launchers opt in for --
+		// nothing to refuse either; FHT: maxdc q 8 bytes, at most
 		// 65,536 B at q = 256 and degree 32, what a launch gets without opting in -- nothing to refuse either)
 		if (params->method == NBL_METHOD_TEMS) {
 			if (!tems_needs_wide && nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
@@ -582,6 +608,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	d->fht = fht;
 	d->ems_wide = ems_wide;
 	d->tems_wide = tems_wide;
+	d->bp_wide = bp_wide;
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;

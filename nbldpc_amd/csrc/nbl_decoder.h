@@ -76,6 +76,7 @@ struct nbl_decoder {
 	bool fht = false;         // nbl_create_fht: the FHT sum-product check node in place of the exact one (flooding or layered)
 	bool ems_wide = false;    // nbl_create_ems_wide: EMS with check degrees up to NBL_EMS_MAX_CHECK_DEGREE (flooding or layered)
 	bool tems_wide = false;   // nbl_create_tems_wide: T-EMS with check degrees up to NBL_TEMS_MAX_CHECK_DEGREE over any field (flooding or layered)
+	bool bp_wide = false;     // nbl_create_bp_wide: exact log-QSPA with check degrees up to NBL_BP_MAX_CHECK_DEGREE (flooding or layered)
 	int n_layers = 0;
 	std::vector<int> h_layer_of; // [M] the assignment in use
 	std::vector<int> h_lay_off;  // [n_layers + 1] offsets into ly.chk

@@ -63,6 +63,15 @@ size_t nbl_tems_wide_lds_bytes(int q, int maxdc, int nr, int nc);
 hipError_t nbl_launch_cn_tems_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_tems_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// exact log-QSPA check node for checks up to degree NBL_BP_MAX_CHECK_DEGREE (nbl_create_bp_wide; nbl_cn_bp_wide.hip): the programme of
+// nbl_cn_bp_wide_core.h, one check per workgroup of max(1, q / 64) waves, flooding and the checks of one layer.  LDS of one workgroup:
+// (maxdc + 5) q 8 + 256 bytes, at most 76,032 B (q = 256, degree 32) -- below NBL_BP_WIDE_MAX_LDS for every shape the ABI accepts, so
+// nbl_create_bp_wide refuses no shape for LDS; both launchers size by the one function and check the bound all the same
+#define NBL_BP_WIDE_MAX_LDS (160 * 1024)
+size_t nbl_bp_wide_lds_bytes(int q, int maxdc);
+hipError_t nbl_launch_cn_bp_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_bp_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 size_t nbl_ems256_lds_bytes(int nm);
 hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);

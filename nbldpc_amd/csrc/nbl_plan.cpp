@@ -34,14 +34,22 @@ NblShape nbl_shape(const nbl_code_desc *code)
 static const char *const cn_names[NBL_CN_COUNT] = {
 	"ems256", "ems_small", "ems64", "ems", "tems64", "tems256", "tems_small", "tems", "bp256", "bp64", "bp_small", "bp",
 	"bstems", "ems_layered", "tems_layered", "none", "bp_layered", "fht", "fht_layered", "fht_wide", "fht_wide_layered", "ems_wide", "ems_wide_layered",
-	"tems_wide", "tems_wide_layered"};
+	"tems_wide", "tems_wide_layered", "bp_wide", "bp_wide_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht, bool ems_wide, bool tems_wide)
+                 bool small_on, bool fht, bool ems_wide, bool tems_wide, bool bp_wide)
 {
 	NblPlan pl{NBL_CN_NONE, false, false, true};
+	if (bp_wide && (s.maxdc > NBL_MAXDC || force_generic == 3)) {
+		// the workgroup-per-check programme: never fused; both schedules read v2c (flooding: the inputs; layered: the damping).  With
+		// maxdc <= NBL_MAXDC (switch 3) `fusable` stays that of the decoder's default plan (switch 0), so that the workspace does not move
+		// with a debug switch
+		if (s.maxdc <= NBL_MAXDC) pl.fusable = nbl_plan(s, prm, nbl_params_ext{}, layered, 0, record_state, small_on).fusable;
+		pl.cn = layered ? NBL_CN_BP_WIDE_LAYERED : NBL_CN_BP_WIDE;
+		return pl;
+	}
 	if (tems_wide && (nbl_tems_needs_wide(s) || (force_generic == 3 && prm.tems_nc <= NBL_TEMS_WIDE_MAX_NC))) {
 		// the workgroup-per-check programme: never fused; both schedules read v2c (flooding: the inputs; layered: the damping).  Inside
 		// nbl_create's envelope (switch 3) `fusable` stays that of the decoder's default plan, so that the workspace does not move with a

@@ -14,6 +14,7 @@ enum NblCn {
 	NBL_CN_FHT_WIDE, NBL_CN_FHT_WIDE_LAYERED, // the same in the degree-independent layout: codes with a check above degree NBL_MAXDC
 	NBL_CN_EMS_WIDE, NBL_CN_EMS_WIDE_LAYERED, // nbl_create_ems_wide: EMS, one check per workgroup, any check degree up to NBL_EMS_MAX_CHECK_DEGREE
 	NBL_CN_TEMS_WIDE, NBL_CN_TEMS_WIDE_LAYERED, // nbl_create_tems_wide: T-EMS, one check per workgroup, 64-bit path code, check degrees up to NBL_TEMS_MAX_CHECK_DEGREE
+	NBL_CN_BP_WIDE, NBL_CN_BP_WIDE_LAYERED, // nbl_create_bp_wide: exact log-QSPA, one check per workgroup, check degrees up to NBL_BP_MAX_CHECK_DEGREE
 	NBL_CN_COUNT
 };
 
@@ -33,9 +34,11 @@ NblShape nbl_shape(const nbl_code_desc *code);
 // every switch; any other code gets the plan of nbl_create / nbl_create_layered, except that force_generic 3 selects the wide programme;
 // tems_wide: an nbl_create_tems_wide decoder (method 4): a code with a check above degree NBL_MAXDC or with log2(q) maxdc > 32 (the path
 // does not fit tems_check_node's 32-bit code) runs tems_wide / tems_wide_layered under every switch; any other code gets the plan of
-// nbl_create / nbl_create_layered_ex, except that force_generic 3 selects the wide programme where tems_nc <= NBL_TEMS_WIDE_MAX_NC
+// nbl_create / nbl_create_layered_ex, except that force_generic 3 selects the wide programme where tems_nc <= NBL_TEMS_WIDE_MAX_NC;
+// bp_wide: an nbl_create_bp_wide decoder (method 1): a code with a check above degree NBL_MAXDC runs bp_wide / bp_wide_layered under
+// every switch; any other code gets the plan of nbl_create / nbl_create_layered_bp, except that force_generic 3 selects the wide programme
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht = false, bool ems_wide = false, bool tems_wide = false);
+                 bool small_on, bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false);
 // the codes only the wide T-EMS programme runs (creation refuses tems_nc > NBL_TEMS_WIDE_MAX_NC there)
 inline bool nbl_tems_needs_wide(const NblShape &s) { return s.maxdc > NBL_MAXDC || s.p * s.maxdc > 32; }
 const char *nbl_cn_name(NblCn cn);

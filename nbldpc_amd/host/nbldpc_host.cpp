@@ -158,7 +158,28 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = twide     ? nbl_create_tems_wide(&code, mul.data(), inv.data(), &p, nullptr, damped ? NBL_TEMS_WIDE_LAYERED : 0u, device, &dec)
+	// NBL_BP_WIDE=1: exact log-QSPA through nbl_create_bp_wide, which takes check degrees up to NBL_BP_MAX_CHECK_DEGREE (off by default,
+	// NBL_BP_WIDE=0 names the default).  A log-QSPA profile (method 1) without OSD only; combines with NBL_SCHEDULE=flooding (or unset) and
+	// layered-bp; not with NBL_BP_CHECK=fht, which names another check node
+	const char *bwenv = getenv("NBL_BP_WIDE");
+	const bool bwide = bwenv && std::string(bwenv) == "1";
+	if (bwenv && !bwide && std::string(bwenv) != "0") {
+		error = std::string("NBL_BP_WIDE=") + bwenv + ": unknown value (0, 1)";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (bwide && fht) {
+		error = "NBL_BP_WIDE=1 with NBL_BP_CHECK=fht: the wide log-QSPA decoder runs the exact check node; the FHT check node takes checks up to degree 32 by itself";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (bwide && (sim.decodeMethod != BP_DECODE || osd || wide || twide || (layered && !lay_bp))) {
+		error = "NBL_BP_WIDE=1: the wide log-QSPA decoder is defined for log-QSPA (method 1) without OSD only, under NBL_SCHEDULE=flooding or layered-bp";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	nbl_status st = bwide     ? nbl_create_bp_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_BP_WIDE_LAYERED : 0u, device, &dec)
+	                : twide   ? nbl_create_tems_wide(&code, mul.data(), inv.data(), &p, nullptr, damped ? NBL_TEMS_WIDE_LAYERED : 0u, device, &dec)
 	                : wide    ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)
 	                : fht     ? nbl_create_fht(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT_LAYERED : 0u, device, &dec)
 	                : lay_bp  ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
