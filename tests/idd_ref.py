@@ -7,7 +7,7 @@ probability-domain brute force of the prior-aware demodulator, and two anchors w
   demod_prior(...)       the prior-aware general demodulator, float64 or numpy.longdouble; frames are the only vectorised axis
   brute_force(...)       the same LLRs from probabilities: P(c) = prod sigmoid(+-prior), sum over c of P(c) exp(-d / 2 sigma^2)
   extrinsic_bits(...)    NBL_SOFT_EXTRINSIC: soft_ref.posterior from the all-0.0 vector, then soft_ref.bit_marginals
-  loop(...)              the loop on the canonical oracle, one codeword at a time
+  loop(...)              the loop around a decode of one codeword (the canonical oracle's, or any callable of the same form)
   loop_cell(...)         the cells both test files walk, their samples and their oracle results (computed once)
 """
 import functools
@@ -228,10 +228,21 @@ def extrinsic_bits(c2v_vm, graph, q, metric, dtype=np.float64):
     return P, sr.bit_marginals(P, q.bit_length() - 1, metric, dtype)
 
 
-def loop(od, graph, sh, rx, sigma, demod_metric, passes, soft_metric):
-    """The loop of include/nbldpc.h on the canonical oracle `od` (a pyoracle.Decoder under early exit):
+def oracle_decode(od):
+    """the decode callable loop() takes, on a canonical oracle `od` (a pyoracle.Decoder under early exit): its decoder and its state"""
+    def decode(L):
+        r, o, it = od.decode(L)
+        return int(r), o, int(it), od.state()[2]
+    return decode
+
+
+def loop(decode, graph, sh, rx, sigma, demod_metric, passes, soft_metric):
+    """The loop of include/nbldpc.h around `decode`, a callable L_ch [N][q-1] -> (converged, out [N], iters, c2v [E][q-1] variable-major)
+    of one codeword from zero messages, or a pyoracle.Decoder under early exit (then oracle_decode of it):
     (out [B][N], converged [B], iters [B], passes_used [B]).  Codewords are independent; the frames still unconverged share one call
     of the restatement per pass only because frames are its vectorised axis (elementwise arithmetic: the same values as one by one)."""
+    if not callable(decode):
+        decode = oracle_decode(decode)
     B, N, p, q = rx.shape[0], sh["N"], sh["p"], sh["q"]
     out = np.zeros((B, N), dtype=np.int32)
     conv, iters, used = np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
@@ -244,11 +255,11 @@ def loop(od, graph, sh, rx, sigma, demod_metric, passes, soft_metric):
             L, _ = demod_prior(sh["points"], sh["src"], rx[live], sigma, N, p, demod_metric, prior[live])
         left = []
         for row, b in enumerate(live):
-            r, o, it = od.decode(L[row])
+            r, o, it, c2v = decode(L[row])
             if r or k == passes:
                 out[b], conv[b], iters[b], used[b] = o, int(r), int(it), k
             else:
-                prior[b] = extrinsic_bits(od.state()[2], graph, q, soft_metric)[1]
+                prior[b] = extrinsic_bits(c2v, graph, q, soft_metric)[1]
                 left.append(b)
         live = left
         if not live:
