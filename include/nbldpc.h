@@ -294,6 +294,47 @@ nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_m
 nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                           const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 
+/* ---- Single-precision FHT sum-product decoding: FP32 messages, flooding and layered ------------------------------------------------
+ * The FHT decoder above has no reference to match -- it is defined here, operation by operation -- so it is the one decoder kind whose
+ * precision can change without touching a parity statement made against the reference.  nbl_create_fht32 is word for word the FHT decoder
+ * of nbl_create_fht, flooding (flags 0) or layered (NBL_FHT32_LAYERED), with these replacements (tests/fht32_ref.py restates it in
+ * numpy: fht_ref.decode_flooding / decode_layered with dtype = np.float32):
+ *   1. Channel vectors.  Lf[n][a] = (float) L_ch[n][a], round to nearest even, once per decode call.  Every front end (host or device
+ *      LLRs, bit LLRs, the demodulators, priors, gains, the channel) produces the FP64 L_ch it produces on every other decoder; one
+ *      narrowing launch follows it.  Inputs are assumed finite and inside the binary32 range.
+ *   2. Arithmetic.  Everything the iterations compute is IEEE binary32, every product and every sum rounded on its own, no contraction:
+ *      the a-posteriori sum in the variable's edge order starting from Lf, DecideLLRVector on the float vector (the same tie rule),
+ *      raw = P - c2v, the 0.5 / 0.5 per-edge damping where decisions differ, the initial v2c = Lf, and steps 1-7 of the check-node update.
+ *   3. The floor (step 6) is t * 2^-NBL_FHT32_FLOOR_LOG2 = t * 2^-16: no c2v entry lies more than 16 ln 2 = 11.09 nats below its vector's
+ *      largest.  The transform's rounding noise must stay well below the floor, as it does in FP64 (2^-40 against 2^-53): the largest
+ *      |v32 - v80| / t measured on the CPU is 2^-20.7 (q = 256, degree 8), so an entry at the floor carries a relative error of about 2^-5
+ *      (0.03 nats) where the FP64 kind's figure is 2^-10.
+ *   4. exp and log: any evaluation within 2 ulp of binary32 (the device library's expf / logf qualify; a bare hardware exp2 on
+ *      x * log2(e) does not for |x| above about 8, where the product's rounding alone is |x| 2^-24 relative).
+ *   5. Limits.  Check degrees 2 .. 8, variable degrees 1 .. 8: |U[y]| <= q, so a product of up to 7 transformed vectors stays below 2^56
+ *      and its transform below 2^64; at degree 32 it would leave binary32's range.  A larger check is NBL_ERR_ARG (the message names
+ *      nbl_create_fht32, the degree found and 8, and points to nbl_create_fht).  Any method but 1 is NBL_ERR_UNSUPPORTED (the message names
+ *      method 1); an unknown flag bit is NBL_ERR_ARG; a non-NULL layer_of with flags 0 is NBL_ERR_ARG; every assignment error of
+ *      nbl_create_layered keeps its status and text; everything else nbl_create refuses is refused the same way.  No OSD, no extension
+ *      parameters.  All of it before the device is touched.
+ *   6. State and soft output.  nbl_read_state returns post (with nbl_set_record_state), c2v and v2c as doubles that are the EXACT widening
+ *      of the float state; order and early-exit rules are the FHT kind's.  nbl_soft_output* keeps its definition unchanged: P = L_ch (the
+ *      caller's FP64 vector, not Lf) plus the c2v exactly as nbl_read_state returns them, summed in double -- bit for bit the sum above
+ *      over this decoder's own read_state.  The iterative-demapping loop, a chain of public calls, needs nothing new.
+ *   7. Every decode entry point (host, device, bits, samples, prior, csi, idd, resident, noise), fixed_iters, poll_every and the active
+ *      list, the transmitter, channel, fading and error count work unchanged on such a decoder; nbl_get_layers works on the layered kind
+ *      and is NBL_ERR_ARG on the flooding kind.  The FP64 copies of c2v / v2c / post exist from the first call that reads the state
+ *      (nbl_read_state, nbl_soft_output*, a demapping loop of several passes) and count in nbl_workspace_bytes from then on.
+ *   8. Parity, the method's own.  Hard decisions, converged flags and iteration counts equal those of the float32 numpy restatement on
+ *      inputs whose decisions have a margin; for post, c2v and v2c, |w(x_gpu) - w(x_ref)| stays within 16 x D32, the case's recorded
+ *      deviation between two evaluations of the restatement: numpy's float32 exp / log, and exp / log taken in float64 and rounded once
+ *      to float32 (how far one rounding of exp / log moves the state: the only place implementations may differ).  Nothing is claimed
+ *      about closeness to the FP64 kind; DESIGN.md section 5q records what was measured. */
+#define NBL_FHT32_FLOOR_LOG2 16
+#define NBL_FHT32_LAYERED 1u
+nbl_status nbl_create_fht32(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                            const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
 /* ---- EMS decoding for high-rate codes: check degrees up to 32, flooding and layered ------------------------------------------------
  * nbl_create_ems_wide: NBL_METHOD_EMS only (no OSD, no extension parameters).  There is no new arithmetic: a check's output is the
  * canonical, residue-free EMS value defined above (the maximum over conf(q,1) U conf(nm,nc) of the left-to-right sums over the other

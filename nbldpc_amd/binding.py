@@ -18,6 +18,7 @@ DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
 SOFT_EXTRINSIC = 1
 FHT_LAYERED = 1          # NBL_FHT_LAYERED
+FHT32_LAYERED = 1        # NBL_FHT32_LAYERED
 EMS_WIDE_LAYERED = 1     # NBL_EMS_WIDE_LAYERED
 TEMS_WIDE_LAYERED = 1    # NBL_TEMS_WIDE_LAYERED
 BP_WIDE_LAYERED = 1      # NBL_BP_WIDE_LAYERED
@@ -106,6 +107,8 @@ def load_library():
         L.nbl_create_layered_bp.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_create_fht.restype = C.c_int
         L.nbl_create_fht.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        L.nbl_create_fht32.restype = C.c_int
+        L.nbl_create_fht32.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_create_ems_wide.restype = C.c_int
         L.nbl_create_ems_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_create_tems_wide.restype = C.c_int
@@ -200,21 +203,29 @@ class PlanInfo(C.Structure):
 
 
 def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=None, bs_nc=2, layers=None, damped=None,
-               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False):
+               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False):
     """The check-node kernel a decoder of this description would run (nbl_debug_plan; host arithmetic, no device, no decoder):
     (kernel name, fusable, fused, want_v2c).  The description is built the way Decoder builds it; layers / damped / fht as there
     (None = flooding), force_generic as nbl_debug_force_generic takes it (with fht, 3 names the wide programme, fht_wide /
     fht_wide_layered, at any check degree; with wide, the decoder nbl_create_ems_wide would make: 3 names ems_wide / ems_wide_layered at
     any check degree; with tems_wide, the decoder nbl_create_tems_wide would make: 3 names tems_wide / tems_wide_layered at any check
     degree where tems_nc <= 4; with bp_wide, the decoder nbl_create_bp_wide would make: 3 names bp_wide / bp_wide_layered at any check
-    degree), record_state as nbl_set_record_state.  fht, wide, tems_wide and bp_wide exclude one another."""
-    if sum(map(bool, (fht, wide, tems_wide, bp_wide))) > 1:
-        raise ValueError("fht, wide, tems_wide and bp_wide name four different entry points: give one of them")
+    degree; with fht32, the decoder nbl_create_fht32 would make: fht32 / fht32_layered under every switch), record_state as
+    nbl_set_record_state.  fht, wide, tems_wide, bp_wide and fht32 exclude one another."""
+    if sum(map(bool, (fht, wide, tems_wide, bp_wide, fht32))) > 1:
+        raise ValueError("fht, wide, tems_wide, bp_wide and fht32 name five different entry points: give one of them")
     lib = load_library()
     params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
     ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
     desc = code.desc()
     out = PlanInfo()
+    if fht32:
+        lib.nbl_debug_plan_fht32.restype = C.c_int
+        lib.nbl_debug_plan_fht32.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
+        rc = lib.nbl_debug_plan_fht32(C.byref(desc), C.byref(params), 0 if layers is None else FHT32_LAYERED, force_generic, int(record_state), C.byref(out))
+        if rc != 0:
+            raise NblError(rc, "nbl_debug_plan_fht32")
+        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
     if bp_wide:
         lib.nbl_debug_plan_bp_wide.restype = C.c_int
         lib.nbl_debug_plan_bp_wide.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
@@ -271,12 +282,15 @@ class Decoder:
     layers) or of nbl_create_layered_ex with NBL_LAYERED_DAMPED (layers="greedy" or an assignment) with check degrees up to
     NBL_TEMS_MAX_CHECK_DEGREE = 32 over any field and tems_nc up to 4 there.  bp_wide=True (method 1 only; without fht, wide, tems_wide,
     damped, bp, OSD or extension parameters): nbl_create_bp_wide, the exact log-QSPA decoder of nbl_create (without layers) or of
-    nbl_create_layered_bp (layers="greedy" or an assignment) with check degrees up to NBL_BP_MAX_CHECK_DEGREE = 32."""
+    nbl_create_layered_bp (layers="greedy" or an assignment) with check degrees up to NBL_BP_MAX_CHECK_DEGREE = 32.  fht32=True (method 1
+    only; without fht, bp, damped, wide, tems_wide, bp_wide, OSD or extension parameters): nbl_create_fht32, the FHT decoder in single
+    precision -- float messages, the floor at 2^-16, check degrees up to 8 -- flooding without layers, layered with layers="greedy" or an
+    assignment; read_state and soft_output return doubles that are the exact widening of the float state."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False):
+                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -304,6 +318,9 @@ class Decoder:
         if bp_wide and (bp or damped is not None or osd_order is not None or bs_nm is not None):
             raise ValueError("bp_wide: nbl_create_bp_wide takes no damped / bp flag and neither OSD nor extension parameters (layers alone picks its schedule; "
                              "the layered one is that of nbl_create_layered_bp)")
+        if fht32 and (fht or bp or damped is not None or wide or tems_wide or bp_wide or osd_order is not None or bs_nm is not None):
+            raise ValueError("fht32: nbl_create_fht32 takes no fht / bp / damped / wide / tems_wide / bp_wide flag and neither OSD nor extension parameters "
+                             "(layers alone picks its schedule)")
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
                 raise ValueError("layers: nbl_create_layered takes neither OSD nor extension parameters")
@@ -311,7 +328,9 @@ class Decoder:
             if self._layer_of is not None and self._layer_of.shape != (code.M,):
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
             lay = None if self._layer_of is None else self._layer_of.ctypes.data
-            if bp_wide:
+            if fht32:
+                rc = self.lib.nbl_create_fht32(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, FHT32_LAYERED, device, C.byref(h))
+            elif bp_wide:
                 rc = self.lib.nbl_create_bp_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, BP_WIDE_LAYERED, device, C.byref(h))
             elif tems_wide:
                 rc = self.lib.nbl_create_tems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, TEMS_WIDE_LAYERED, device, C.byref(h))
@@ -326,6 +345,8 @@ class Decoder:
             else:
                 rc = self.lib.nbl_create_layered_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,
                                                     int(damped), device, C.byref(h))
+        elif fht32:
+            rc = self.lib.nbl_create_fht32(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
         elif bp_wide:
             rc = self.lib.nbl_create_bp_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
         elif tems_wide:

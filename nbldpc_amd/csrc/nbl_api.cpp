@@ -25,6 +25,8 @@ static void free_workspace(nbl_decoder *d)
 	d->w.dec = d->w.out = d->w.iters = d->w.edge_dec = nullptr;
 	d->w.done = nullptr;
 	d->w.active = nullptr;
+	d->w32 = NblWork32{};
+	d->wide_valid = false;
 	d->cap = 0;
 	d->last_B = 0; // (nothing of the last decode call is left to read)
 	d->last_c2v = nullptr;
@@ -39,11 +41,64 @@ static bool small_enabled()
 // The kernel choice of this decoder as it stands (nbl_plan.cpp): once per workspace check and once per decode, never per launch
 static NblPlan plan_of(const nbl_decoder *d)
 {
-	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled(), d->fht, d->ems_wide, d->tems_wide, d->bp_wide);
+	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled(), d->fht, d->ems_wide, d->tems_wide, d->bp_wide, d->fht32);
+}
+
+// nbl_create_fht32: the FP64 L_ch every front end fills, the float state the iterations run on, decisions and flags.  The FP64 c2v /
+// v2c / post are not made here (widen_state makes them for the first FP64 reader of the state).
+static nbl_status ensure_workspace32(nbl_decoder *d, int B)
+{
+	const bool want_post = d->record_state;
+	if (B <= d->cap && (!want_post || d->w32.post)) return NBL_OK;
+	const int cap = B > d->cap ? B : d->cap;
+	free_workspace(d);
+	const size_t q = d->g.q, N = d->g.N, E = d->g.E;
+	nbl_decoder::Ws &b = d->ws;
+	nbl_status s = NBL_OK;
+	auto make = [&](auto &buf, bool want, size_t n) { if (!s && want) s = buf.grow(d->err, n); };
+	make(b.Lch, true, (size_t)cap * N * q * 8);
+	make(b.Lf, true, (size_t)cap * N * q * 4);
+	make(b.v2c32, true, (size_t)cap * E * q * 4);
+	make(b.c2v32, true, (size_t)cap * E * q * 4);
+	make(b.post32, want_post, (size_t)cap * N * q * 4);
+	make(b.dec, true, (size_t)cap * N * 4);
+	make(b.out, true, (size_t)cap * N * 4);
+	make(b.iters, true, (size_t)cap * 4);
+	make(b.done, true, (size_t)cap);
+	make(b.active, true, (size_t)cap * 4);
+	if (s) { free_workspace(d); return s; }
+	d->w.Lch = b.Lch;
+	d->w.dec = b.dec; d->w.out = b.out; d->w.iters = b.iters; d->w.done = b.done;
+	d->w32 = NblWork32{b.Lf, b.v2c32, b.c2v32, b.post32};
+	d->cap = cap;
+	return NBL_OK;
+}
+
+nbl_status widen_state(nbl_decoder *d, hipStream_t reader)
+{
+	if (!d->fht32 || d->last_B <= 0 || !d->w32.c2v) return NBL_OK;
+	hipStream_t st = reader ? reader : d->stream;
+	if (d->wide_valid && d->wide_stream == st) return NBL_OK;
+	const size_t q = d->g.q, N = d->g.N, E = d->g.E, cap = (size_t)d->cap;
+	nbl_decoder::Ws &b = d->ws;
+	nbl_status s;
+	if ((s = b.c2v.grow(d->err, cap * E * q * 8)) || (s = b.v2c.grow(d->err, cap * E * q * 8))) return s;
+	if (d->w32.post && (s = b.post.grow(d->err, cap * N * q * 8))) return s;
+	d->w.c2v = b.c2v; d->w.v2c = b.v2c;
+	d->w.post = d->w32.post ? b.post.p : nullptr; // (what the last decode did not record is not read: nbl_read_state's rule)
+	d->last_c2v = d->w.c2v;
+	const long long B = d->last_B;
+	HIP_TRY(d, nbl_launch_widen32(d->w32.c2v, d->w.c2v, B * (long long)(E * q), st));
+	HIP_TRY(d, nbl_launch_widen32(d->w32.v2c, d->w.v2c, B * (long long)(E * q), st));
+	if (d->w.post) HIP_TRY(d, nbl_launch_widen32(d->w32.post, d->w.post, B * (long long)(N * q), st));
+	d->wide_valid = true;
+	d->wide_stream = st;
+	return NBL_OK;
 }
 
 nbl_status ensure_workspace(nbl_decoder *d, int B)
 {
+	if (d->fht32) return ensure_workspace32(d, B);
 	const NblPlan plan = plan_of(d);
 	const bool want_v2c = plan.want_v2c;
 	const bool want_post = d->record_state || d->osd_acc;
@@ -214,6 +269,17 @@ extern "C" nbl_status nbl_debug_plan_fht(const nbl_code_desc *code, const nbl_pa
 	return NBL_OK;
 }
 
+// The same for a decoder nbl_create_fht32 would make; fht_flags: NBL_FHT32_* of include/nbldpc.h
+extern "C" nbl_status nbl_debug_plan_fht32(const nbl_code_desc *code, const nbl_params *params, uint32_t fht_flags, int32_t force_generic, int32_t record_state,
+                                           nbl_plan_info *out)
+{
+	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
+	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (fht_flags & NBL_FHT32_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), false, false,
+	                              false, false, true);
+	*out = {nbl_plan_name(plan), plan.fusable, plan.fused, plan.want_v2c};
+	return NBL_OK;
+}
+
 // The same for a decoder nbl_create_ems_wide would make; wide_flags: NBL_EMS_WIDE_* of include/nbldpc.h
 extern "C" nbl_status nbl_debug_plan_ems_wide(const nbl_code_desc *code, const nbl_params *params, uint32_t wide_flags, int32_t force_generic, int32_t record_state,
                                               nbl_plan_info *out)
@@ -291,7 +357,10 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_BP64: HIP_TRY(d, nbl_launch_cn_bp64(g, w, r, fused, st)); break;
 	case NBL_CN_BP_SMALL: HIP_TRY(d, nbl_launch_cn_bp_small(g, w, r, fused, st)); break;
 	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
-	case NBL_CN_FHT: HIP_TRY(d, nbl_launch_cn_fht(g, w, r, st)); break;
+	case NBL_CN_FHT:
+		if (d->fht32) HIP_TRY(d, nbl_launch_cn_fht32(g, w, d->w32, r, st)); // (NblPlan::f32: the binary32 instance on the float state)
+		else HIP_TRY(d, nbl_launch_cn_fht(g, w, r, st));
+		break;
 	case NBL_CN_FHT_WIDE: HIP_TRY(d, nbl_launch_cn_fht_wide(g, w, r, st)); break;
 	case NBL_CN_EMS_WIDE: HIP_TRY(d, nbl_launch_cn_ems_wide(g, w, r, st)); break;
 	case NBL_CN_TEMS_WIDE: HIP_TRY(d, nbl_launch_cn_tems_wide(g, w, r, st)); break;
@@ -347,7 +416,8 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 		if (d->layered) {
 			// decision and syndrome from the c2v the previous iteration left, then the layers in order, each on the c2v the layers
 			// before it have just written (one buffer; the launches of a stream run in order)
-			HIP_TRY(d, nbl_launch_vn_decide(d->g, d->w, c.r, st));
+			if (d->fht32) HIP_TRY(d, nbl_launch_vn32(d->g, d->w, d->w32, c.r, false, st)); // (the same pass on the float state)
+			else HIP_TRY(d, nbl_launch_vn_decide(d->g, d->w, c.r, st));
 			HIP_TRY(d, mark(c, 0, st));
 			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
 			HIP_TRY(d, mark(c, 1, st));
@@ -359,7 +429,10 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 				case NBL_CN_EMS_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_TEMS_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_BP_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_FHT_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
+				case NBL_CN_FHT_LAYERED:
+					if (d->fht32) HIP_TRY(d, nbl_launch_cn_fht32_layered(d->g, d->w, d->w32, c.r, d->ly, off, cnt, st));
+					else HIP_TRY(d, nbl_launch_cn_fht_layered(d->g, d->w, c.r, d->ly, off, cnt, st));
+					break;
 				case NBL_CN_EMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_TEMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
 				case NBL_CN_BP_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
@@ -403,7 +476,8 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			if (count) { d->launches[2]++; d->launches[1]++; }
 			continue;
 		}
-		HIP_TRY(d, nbl_launch_vn(d->g, d->w, c.r, c.damp, st));
+		if (d->fht32) HIP_TRY(d, nbl_launch_vn32(d->g, d->w, d->w32, c.r, true, st)); // (the same pass, damped, on the float state)
+		else HIP_TRY(d, nbl_launch_vn(d->g, d->w, c.r, c.damp, st));
 		HIP_TRY(d, mark(c, 0, st));
 		if (d->osd_acc) {
 			HIP_TRY(d, nbl_launch_osd_acc(d->w.post, d->ws.osd_S, c.batch, d->g.N, d->g.p, d->g.q, d->osd_factor, it == 1, st));
@@ -484,8 +558,15 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 	c.batch = B;
 	if (memcmp(&key, &d->gkey, sizeof key) != 0) { drop_graphs(d); d->gkey = key; }
 	HIP_TRY(d, mark(c, 3, st));
-	HIP_TRY(d, nbl_launch_init(d_Lin, d->g, d->w, B, (c.damp ? 1 : 0) | (c.zeros ? 2 : 0), st)); // bit 1: c2v is not cleared
+	// (nbl_create_fht32: L_ch and the flags alone -- no FP64 message buffer need exist; then the one narrowing launch of the call, which
+	// also sets the float v2c = Lf and c2v = 0.  Its time is in ms[3] alone: nbl_last_timing has no launch counter for it)
+	HIP_TRY(d, nbl_launch_init(d_Lin, d->g, d->w, B, d->fht32 ? 2 : (c.damp ? 1 : 0) | (c.zeros ? 2 : 0), st)); // bit 1: c2v is not cleared
 	HIP_TRY(d, mark(c, 3, st));
+	if (d->fht32) {
+		HIP_TRY(d, nbl_launch_narrow32(d->g, d->w.Lch, d->w32, B, st));
+		HIP_TRY(d, mark(c, 3, st));
+		d->wide_valid = false;
+	}
 	d->last_c2v = c.zeros ? c.zeros : c.bufA;
 	d->last_fused = c.plan.fused;
 	// windows: fixed iterations or no polling -> one window; early exit -> `poll_every` iterations, then ask the device
@@ -660,6 +741,7 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 	d->err.clear();
 	HIP_TRY(d, hipSetDevice(d->device));
 	const int q = d->g.q, N = d->g.N, E = d->g.E;
+	if (nbl_status s = widen_state(d)) return s; // (nbl_create_fht32: the doubles below are the exact widening of the float state)
 	DevBuf<double> tmp;
 	if (nbl_status s = tmp.grow(d->err, (size_t)E * (q - 1) * 8)) return s;
 	nbl_status rc = NBL_OK;

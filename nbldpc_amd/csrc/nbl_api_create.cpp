@@ -247,7 +247,7 @@ struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out,
-                              bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false);
+                              bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false, bool fht32 = false);
 
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
@@ -290,6 +290,21 @@ extern "C" nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *
 		                                         "NBL_FHT_LAYERED)");
 	const LayerReq lay = {layer_of, 0, true};
 	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_FHT_LAYERED) ? &lay : nullptr, device, out, true);
+}
+
+// Single-precision FHT sum-product decoding (include/nbldpc.h): the requests of nbl_create_fht, a float message state, checks up to degree 8
+extern "C" nbl_status nbl_create_fht32(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                       const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	if (!out) return NBL_ERR_ARG;
+	*out = nullptr;
+	if (flags & ~(uint32_t)NBL_FHT32_LAYERED)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht32: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_FHT32_LAYERED = 1 is the only one defined)");
+	if (!(flags & NBL_FHT32_LAYERED) && layer_of)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht32: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or set "
+		                                         "NBL_FHT32_LAYERED)");
+	const LayerReq lay = {layer_of, 0, true};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_FHT32_LAYERED) ? &lay : nullptr, device, out, false, false, false, false, true);
 }
 
 // EMS with check degrees up to NBL_EMS_MAX_CHECK_DEGREE (include/nbldpc.h): flooding without a LayerReq, layered with the request of
@@ -350,7 +365,7 @@ extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, in
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht, bool ems_wide,
-                              bool tems_wide, bool bp_wide)
+                              bool tems_wide, bool bp_wide, bool fht32)
 {
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
@@ -366,6 +381,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
 	if (fht && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_fht runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, "
+		                                                 "which no other method's check node is");
+	if (fht32 && params->method != NBL_METHOD_BP)
+		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_fht32 runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, "
 		                                                 "which no other method's check node is");
 	if (ems_wide && params->method != NBL_METHOD_EMS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide runs EMS (method 2) only: the other methods keep their entry points and their check-degree "
@@ -470,6 +488,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (fht && maxdv <= NBL_MAXDV && maxdc > NBL_FHT_MAX_CHECK_DEGREE)
 		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
 		                                         std::to_string(NBL_FHT_MAX_CHECK_DEGREE) + ")");
+	// (nbl_create_fht32: the product of up to 7 transformed vectors and its transform stay inside binary32's range; no wide layout)
+	if (fht32 && maxdv <= NBL_MAXDV && maxdc > NBL_MAXDC)
+		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht32: check degree " + std::to_string(maxdc) + " above the supported maximum (" + std::to_string(NBL_MAXDC) +
+		                                         "): products of more transformed vectors leave the range of single precision; nbl_create_fht (double precision) takes "
+		                                         "check degrees up to " + std::to_string(NBL_FHT_MAX_CHECK_DEGREE));
 	// (nbl_create_ems_wide: one workgroup per check, no array sized by the degree; the limit is the header's, the LDS bound is checked below)
 	if (ems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_EMS_MAX_CHECK_DEGREE)
 		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
@@ -606,6 +629,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		d->h_lay_off = lay_off;
 	}
 	d->fht = fht;
+	d->fht32 = fht32;
 	d->ems_wide = ems_wide;
 	d->tems_wide = tems_wide;
 	d->bp_wide = bp_wide;

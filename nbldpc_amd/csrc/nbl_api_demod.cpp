@@ -277,6 +277,7 @@ extern "C" nbl_status nbl_soft_output_device_ex(nbl_decoder *d, int32_t metric, 
 	HIP_TRY(d, hipSetDevice(d->device));
 	hipStream_t st = stream ? (hipStream_t)stream : d->stream;
 	if ((s = finish_pending(d, st))) return s;
+	if ((s = widen_state(d, st))) return s;
 	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, d_sym_llr, d_bit_llr, st, (flags & NBL_SOFT_EXTRINSIC) != 0));
 	return NBL_OK;
 }
@@ -297,6 +298,7 @@ extern "C" nbl_status nbl_soft_output_ex(nbl_decoder *d, int32_t metric, uint32_
 	if (sym_llr && (s = d->d_soft_sym.grow(d->err, sym_bytes))) return s;
 	if (bit_llr && (s = d->d_soft_bit.grow(d->err, bit_bytes))) return s;
 	if ((s = finish_pending(d))) return s;
+	if ((s = widen_state(d))) return s;
 	HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), d->last_B, metric, sym_llr ? d->d_soft_sym.p : nullptr,
 	                                  bit_llr ? d->d_soft_bit.p : nullptr, d->stream, (flags & NBL_SOFT_EXTRINSIC) != 0));
 	if (sym_llr) HIP_TRY(d, hipMemcpyAsync(sym_llr, d->d_soft_sym, sym_bytes, hipMemcpyDeviceToHost, d->stream));
@@ -361,6 +363,7 @@ nbl_status run_idd(nbl_decoder *d, const double *d_rx0, double sigma, int B, con
 		if ((s = x.rx[side].grow(d->err, (size_t)live * rx_row * 8))) return s;
 		if ((s = x.idx[side].grow(d->err, (size_t)live * 4))) return s;
 		if ((s = finish_pending(d))) return s; // (the survivors' extrinsic LLRs come from the c2v of the last iteration)
+		if ((s = widen_state(d))) return s;    // (nbl_create_fht32: that c2v, widened, as nbl_soft_output would read it)
 		HIP_TRY(d, nbl_launch_soft_output(d->g, d->w.Lch, soft_src(d), n, idd->soft_metric, nullptr, x.ext, d->stream, true));
 		if (gain && (s = x.gain[side].grow(d->err, (size_t)live * rx_row * 8))) return s;
 		HIP_TRY(d, nbl_launch_idd_gather(d->ws.active, live, rx, rx_row, x.ext, Np, idx, x.rx[side], x.prior, x.idx[side], d->stream, gain,

@@ -74,6 +74,12 @@ struct NblWork {
 	unsigned long long *stamps;     // [NBL_STAMP_SLOTS] debug: per-section cycle sums of the check-node kernel (NULL = off)
 };
 
+// single-precision FHT decoding (nbl_create_fht32): the float message state its kernels run on, beside NblWork (which keeps the FP64
+// L_ch, the decisions and the flags).  Layouts as above with 4-byte entries: Lf [B][N][q], v2c and c2v [B][E][q], post [B][N][q].
+struct NblWork32 {
+	float *Lf, *v2c, *c2v, *post; // post only when state recording is on
+};
+
 // layered (check-serial) schedule, nbl_create_layered (nbl_cn_layered.hip)
 #define NBL_LAYER_ROW 12
 struct NblLayerDev {

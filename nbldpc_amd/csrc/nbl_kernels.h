@@ -46,6 +46,17 @@ hipError_t nbl_launch_cn_fht_layered(const NblGraphDev &g, const NblWork &w, con
 hipError_t nbl_launch_cn_fht_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_fht_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// single-precision FHT decoding (nbl_create_fht32).  nbl_cn_fht32.hip: the programme of nbl_cn_fht32_core.h on the float state `f`,
+// flooding and the checks of one layer, checks up to degree NBL_MAXDC; LDS: maxdc q 4 bytes, at most 8 KB.  nbl_fht32.hip: Lf = (float)
+// L_ch with the initial v2c = Lf and c2v = 0 (one launch per decode call); the float variable-node pass (write_v2c: with the damped v2c
+// half, the flooding schedule; without it, the decision pass of the layered schedule); dst[i] = (double) src[i], i < n
+hipError_t nbl_launch_cn_fht32(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_fht32_layered(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, const NblLayerDev &ly, int offset, int count,
+                                       hipStream_t st);
+hipError_t nbl_launch_narrow32(const NblGraphDev &g, const double *d_Lch, const NblWork32 &f, int B, hipStream_t st);
+hipError_t nbl_launch_vn32(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, bool write_v2c, hipStream_t st);
+hipError_t nbl_launch_widen32(const float *src, double *dst, long long n, hipStream_t st);
+
 // EMS check node for checks up to degree NBL_EMS_MAX_CHECK_DEGREE (nbl_create_ems_wide; nbl_cn_ems_wide.hip): the programme of
 // nbl_cn_ems_wide_core.h, one check per workgroup of max(1, q / 64) waves, flooding and the checks of one layer.  The bytes of LDS of one
 // workgroup are pure arithmetic: nbl_create_ems_wide refuses above NBL_EMS_WIDE_MAX_LDS before the device, both launchers size by it

@@ -37,11 +37,17 @@ static const char *const cn_names[NBL_CN_COUNT] = {
 	"tems_wide", "tems_wide_layered", "bp_wide", "bp_wide_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
+const char *nbl_plan_name(const NblPlan &plan) { return !plan.f32 ? cn_names[plan.cn] : plan.cn == NBL_CN_FHT_LAYERED ? "fht32_layered" : "fht32"; }
 
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht, bool ems_wide, bool tems_wide, bool bp_wide)
+                 bool small_on, bool fht, bool ems_wide, bool tems_wide, bool bp_wide, bool fht32)
 {
-	NblPlan pl{NBL_CN_NONE, false, false, true};
+	NblPlan pl{NBL_CN_NONE, false, false, true, false};
+	if (fht32) { // one general kernel per schedule: never fused; both schedules read the float v2c; no debug switch moves it
+		pl.cn = layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT;
+		pl.f32 = true;
+		return pl;
+	}
 	if (bp_wide && (s.maxdc > NBL_MAXDC || force_generic == 3)) {
 		// the workgroup-per-check programme: never fused; both schedules read v2c (flooding: the inputs; layered: the damping).  With
 		// maxdc <= NBL_MAXDC (switch 3) `fusable` stays that of the decoder's default plan (switch 0), so that the workspace does not move

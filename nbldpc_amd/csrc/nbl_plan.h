@@ -23,6 +23,7 @@ struct NblPlan {
 	bool fusable;  // the shape has a fused iteration (variable-node pass inside cn): c2v_alt and c2v_zero exist
 	bool fused;    // this decode runs it
 	bool want_v2c; // v2c exists in HBM: something reads it (the unfused path, the damped methods, state read-back)
+	bool f32;      // nbl_create_fht32: cn (fht or fht_layered) is run by its binary32 instance on the float message state; named fht32 / fht32_layered
 };
 
 NblShape nbl_shape(const nbl_code_desc *code);
@@ -36,12 +37,15 @@ NblShape nbl_shape(const nbl_code_desc *code);
 // does not fit tems_check_node's 32-bit code) runs tems_wide / tems_wide_layered under every switch; any other code gets the plan of
 // nbl_create / nbl_create_layered_ex, except that force_generic 3 selects the wide programme where tems_nc <= NBL_TEMS_WIDE_MAX_NC;
 // bp_wide: an nbl_create_bp_wide decoder (method 1): a code with a check above degree NBL_MAXDC runs bp_wide / bp_wide_layered under
-// every switch; any other code gets the plan of nbl_create / nbl_create_layered_bp, except that force_generic 3 selects the wide programme
+// every switch; any other code gets the plan of nbl_create / nbl_create_layered_bp, except that force_generic 3 selects the wide programme;
+// fht32: an nbl_create_fht32 decoder (method 1; `layered` says which of its two schedules): the check-node kinds fht / fht_layered in
+// binary32 (NblPlan::f32), never fused, with v2c (the float one); no debug switch moves it
 NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false);
+                 bool small_on, bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false, bool fht32 = false);
 // the codes only the wide T-EMS programme runs (creation refuses tems_nc > NBL_TEMS_WIDE_MAX_NC there)
 inline bool nbl_tems_needs_wide(const NblShape &s) { return s.maxdc > NBL_MAXDC || s.p * s.maxdc > 32; }
 const char *nbl_cn_name(NblCn cn);
+const char *nbl_plan_name(const NblPlan &plan); // nbl_cn_name(plan.cn), or fht32 / fht32_layered for a binary32 plan
 
 // What each specialised kernel can run, beside the kernel (its LDS arithmetic lives there); nbl_plan is the only caller.
 // method: NBL_METHOD_* of include/nbldpc.h.  Unfused: any variable degrees.  Fused: NblShape::has_c_nbr for the small-field and the

@@ -118,14 +118,15 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	// NBL_BP_CHECK=fht: the FHT sum-product check node in place of the exact one (nbl_create_fht; off by default, NBL_BP_CHECK=exact names
 	// the default).  A log-QSPA profile (method 1) without OSD only; combines with NBL_SCHEDULE=flooding (or unset) and layered-bp
 	const char *bpc = getenv("NBL_BP_CHECK");
-	const bool fht = bpc && std::string(bpc) == "fht";
-	if (bpc && !fht && std::string(bpc) != "exact") {
-		error = std::string("NBL_BP_CHECK=") + bpc + ": unknown check node (exact, fht)";
+	// NBL_BP_CHECK=fht32: the same in single precision (nbl_create_fht32: float messages, check degrees up to 8), under the same two schedules
+	const bool fht = bpc && std::string(bpc) == "fht", fht32 = bpc && std::string(bpc) == "fht32";
+	if (bpc && !fht && !fht32 && std::string(bpc) != "exact") {
+		error = std::string("NBL_BP_CHECK=") + bpc + ": unknown check node (exact, fht, fht32)";
 		std::cerr << error << std::endl;
 		return false;
 	}
-	if (fht && (sim.decodeMethod != BP_DECODE || osd || (layered && !lay_bp))) {
-		error = "NBL_BP_CHECK=fht: the FHT check node is defined for log-QSPA (method 1) without OSD only, under NBL_SCHEDULE=flooding or layered-bp";
+	if ((fht || fht32) && (sim.decodeMethod != BP_DECODE || osd || (layered && !lay_bp))) {
+		error = std::string("NBL_BP_CHECK=") + bpc + ": the FHT check node is defined for log-QSPA (method 1) without OSD only, under NBL_SCHEDULE=flooding or layered-bp";
 		std::cerr << error << std::endl;
 		return false;
 	}
@@ -153,7 +154,7 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	if (twide && (sim.decodeMethod != T_EMS_DECODE || osd || wide || fht || (layered && !damped))) {
+	if (twide && (sim.decodeMethod != T_EMS_DECODE || osd || wide || fht || fht32 || (layered && !damped))) {
 		error = "NBL_TEMS_WIDE=1: the wide T-EMS decoder is defined for T-EMS (method 4) without OSD only, under NBL_SCHEDULE=flooding or layered-damped";
 		std::cerr << error << std::endl;
 		return false;
@@ -168,8 +169,8 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	if (bwide && fht) {
-		error = "NBL_BP_WIDE=1 with NBL_BP_CHECK=fht: the wide log-QSPA decoder runs the exact check node; the FHT check node takes checks up to degree 32 by itself";
+	if (bwide && (fht || fht32)) {
+		error = std::string("NBL_BP_WIDE=1 with NBL_BP_CHECK=") + bpc + ": the wide log-QSPA decoder runs the exact check node; the FHT check node takes checks up to degree 32 by itself";
 		std::cerr << error << std::endl;
 		return false;
 	}
@@ -181,6 +182,7 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	nbl_status st = bwide     ? nbl_create_bp_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_BP_WIDE_LAYERED : 0u, device, &dec)
 	                : twide   ? nbl_create_tems_wide(&code, mul.data(), inv.data(), &p, nullptr, damped ? NBL_TEMS_WIDE_LAYERED : 0u, device, &dec)
 	                : wide    ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)
+	                : fht32   ? nbl_create_fht32(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT32_LAYERED : 0u, device, &dec)
 	                : fht     ? nbl_create_fht(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT_LAYERED : 0u, device, &dec)
 	                : lay_bp  ? nbl_create_layered_bp(&code, mul.data(), inv.data(), &p, nullptr, device, &dec)
 	                : damped  ? nbl_create_layered_ex(&code, mul.data(), inv.data(), &p, nullptr, NBL_LAYERED_DAMPED, device, &dec)
