@@ -22,6 +22,9 @@ FHT32_LAYERED = 1        # NBL_FHT32_LAYERED
 EMS_WIDE_LAYERED = 1     # NBL_EMS_WIDE_LAYERED
 TEMS_WIDE_LAYERED = 1    # NBL_TEMS_WIDE_LAYERED
 BP_WIDE_LAYERED = 1      # NBL_BP_WIDE_LAYERED
+# the entry points that name a decoder kind: the library's name of the kind -> (creation function, its layered flag)
+KIND_ENTRY = {"fht": ("nbl_create_fht", FHT_LAYERED), "fht32": ("nbl_create_fht32", FHT32_LAYERED), "ems_wide": ("nbl_create_ems_wide", EMS_WIDE_LAYERED),
+              "tems_wide": ("nbl_create_tems_wide", TEMS_WIDE_LAYERED), "bp_wide": ("nbl_create_bp_wide", BP_WIDE_LAYERED)}
 FADING_NONE, FADING_RAYLEIGH = 0, 1
 
 # every symbol include/nbldpc.h declares
@@ -105,16 +108,9 @@ def load_library():
         L.nbl_create_layered_ex.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_create_layered_bp.restype = C.c_int
         L.nbl_create_layered_bp.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.nbl_create_fht.restype = C.c_int
-        L.nbl_create_fht.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
-        L.nbl_create_fht32.restype = C.c_int
-        L.nbl_create_fht32.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
-        L.nbl_create_ems_wide.restype = C.c_int
-        L.nbl_create_ems_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
-        L.nbl_create_tems_wide.restype = C.c_int
-        L.nbl_create_tems_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
-        L.nbl_create_bp_wide.restype = C.c_int
-        L.nbl_create_bp_wide.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+        for fn, _ in KIND_ENTRY.values():   # one signature: (code, gf_mul, gf_inv, params, layer_of, flags, device, out)
+            getattr(L, fn).restype = C.c_int
+            getattr(L, fn).argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_get_layers.restype = C.c_int
         L.nbl_get_layers.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         L.nbl_destroy.argtypes = [C.c_void_p]
@@ -212,54 +208,27 @@ def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=No
     degree where tems_nc <= 4; with bp_wide, the decoder nbl_create_bp_wide would make: 3 names bp_wide / bp_wide_layered at any check
     degree; with fht32, the decoder nbl_create_fht32 would make: fht32 / fht32_layered under every switch), record_state as
     nbl_set_record_state.  fht, wide, tems_wide, bp_wide and fht32 exclude one another."""
-    if sum(map(bool, (fht, wide, tems_wide, bp_wide, fht32))) > 1:
+    kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32).items() if on]
+    if len(kinds) > 1:
         raise ValueError("fht, wide, tems_wide, bp_wide and fht32 name five different entry points: give one of them")
     lib = load_library()
     params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
     ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
     desc = code.desc()
     out = PlanInfo()
-    if fht32:
-        lib.nbl_debug_plan_fht32.restype = C.c_int
-        lib.nbl_debug_plan_fht32.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
-        rc = lib.nbl_debug_plan_fht32(C.byref(desc), C.byref(params), 0 if layers is None else FHT32_LAYERED, force_generic, int(record_state), C.byref(out))
-        if rc != 0:
-            raise NblError(rc, "nbl_debug_plan_fht32")
-        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
-    if bp_wide:
-        lib.nbl_debug_plan_bp_wide.restype = C.c_int
-        lib.nbl_debug_plan_bp_wide.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
-        rc = lib.nbl_debug_plan_bp_wide(C.byref(desc), C.byref(params), 0 if layers is None else BP_WIDE_LAYERED, force_generic, int(record_state), C.byref(out))
-        if rc != 0:
-            raise NblError(rc, "nbl_debug_plan_bp_wide")
-        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
-    if tems_wide:
-        lib.nbl_debug_plan_tems_wide.restype = C.c_int
-        lib.nbl_debug_plan_tems_wide.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
-        rc = lib.nbl_debug_plan_tems_wide(C.byref(desc), C.byref(params), 0 if layers is None else TEMS_WIDE_LAYERED, force_generic, int(record_state), C.byref(out))
-        if rc != 0:
-            raise NblError(rc, "nbl_debug_plan_tems_wide")
-        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
-    if wide:
-        lib.nbl_debug_plan_ems_wide.restype = C.c_int
-        lib.nbl_debug_plan_ems_wide.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
-        rc = lib.nbl_debug_plan_ems_wide(C.byref(desc), C.byref(params), 0 if layers is None else EMS_WIDE_LAYERED, force_generic, int(record_state), C.byref(out))
-        if rc != 0:
-            raise NblError(rc, "nbl_debug_plan_ems_wide")
-        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
-    if fht:
-        lib.nbl_debug_plan_fht.restype = C.c_int
-        lib.nbl_debug_plan_fht.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
-        rc = lib.nbl_debug_plan_fht(C.byref(desc), C.byref(params), 0 if layers is None else FHT_LAYERED, force_generic, int(record_state), C.byref(out))
-        if rc != 0:
-            raise NblError(rc, "nbl_debug_plan_fht")
-        return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
-    lib.nbl_debug_plan.restype = C.c_int
-    lib.nbl_debug_plan.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.POINTER(ParamsExt), C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
-    rc = lib.nbl_debug_plan(C.byref(desc), C.byref(params), C.byref(ext) if ext is not None else None,
-                            -1 if layers is None else int(bool(damped)), force_generic, int(record_state), C.byref(out))
+    if kinds:   # the library resolves the name: no enum is mirrored here
+        fn = "nbl_debug_plan_kind"
+        lib.nbl_debug_plan_kind.restype = C.c_int
+        lib.nbl_debug_plan_kind.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
+        rc = lib.nbl_debug_plan_kind(C.byref(desc), C.byref(params), kinds[0].encode(), int(layers is not None), force_generic, int(record_state), C.byref(out))
+    else:
+        fn = "nbl_debug_plan"
+        lib.nbl_debug_plan.restype = C.c_int
+        lib.nbl_debug_plan.argtypes = [C.POINTER(CodeDesc), C.POINTER(Params), C.POINTER(ParamsExt), C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanInfo)]
+        rc = lib.nbl_debug_plan(C.byref(desc), C.byref(params), C.byref(ext) if ext is not None else None,
+                                -1 if layers is None else int(bool(damped)), force_generic, int(record_state), C.byref(out))
     if rc != 0:
-        raise NblError(rc, "nbl_debug_plan")
+        raise NblError(rc, fn)
     return out.cn.decode(), bool(out.fusable), bool(out.fused), bool(out.want_v2c)
 
 
@@ -321,6 +290,7 @@ class Decoder:
         if fht32 and (fht or bp or damped is not None or wide or tems_wide or bp_wide or osd_order is not None or bs_nm is not None):
             raise ValueError("fht32: nbl_create_fht32 takes no fht / bp / damped / wide / tems_wide / bp_wide flag and neither OSD nor extension parameters "
                              "(layers alone picks its schedule)")
+        lay = None
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
                 raise ValueError("layers: nbl_create_layered takes neither OSD nor extension parameters")
@@ -328,33 +298,19 @@ class Decoder:
             if self._layer_of is not None and self._layer_of.shape != (code.M,):
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
             lay = None if self._layer_of is None else self._layer_of.ctypes.data
-            if fht32:
-                rc = self.lib.nbl_create_fht32(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, FHT32_LAYERED, device, C.byref(h))
-            elif bp_wide:
-                rc = self.lib.nbl_create_bp_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, BP_WIDE_LAYERED, device, C.byref(h))
-            elif tems_wide:
-                rc = self.lib.nbl_create_tems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, TEMS_WIDE_LAYERED, device, C.byref(h))
-            elif wide:
-                rc = self.lib.nbl_create_ems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, EMS_WIDE_LAYERED, device, C.byref(h))
-            elif fht:
-                rc = self.lib.nbl_create_fht(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, FHT_LAYERED, device, C.byref(h))
-            elif bp:
-                rc = self.lib.nbl_create_layered_bp(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
-            elif damped is None:
-                rc = self.lib.nbl_create_layered(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
-            else:
-                rc = self.lib.nbl_create_layered_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,
-                                                    int(damped), device, C.byref(h))
-        elif fht32:
-            rc = self.lib.nbl_create_fht32(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
-        elif bp_wide:
-            rc = self.lib.nbl_create_bp_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
-        elif tems_wide:
-            rc = self.lib.nbl_create_tems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
-        elif wide:
-            rc = self.lib.nbl_create_ems_wide(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
-        elif fht:
-            rc = self.lib.nbl_create_fht(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), None, 0, device, C.byref(h))
+        # (at most one of the kinds: every pair is refused above)
+        kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32).items() if on]
+        if kinds:
+            fn, layered_flag = KIND_ENTRY[kinds[0]]
+            rc = getattr(self.lib, fn)(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,
+                                       0 if layers is None else layered_flag, device, C.byref(h))
+        elif layers is not None and bp:
+            rc = self.lib.nbl_create_layered_bp(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
+        elif layers is not None and damped is None:
+            rc = self.lib.nbl_create_layered(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay, device, C.byref(h))
+        elif layers is not None:
+            rc = self.lib.nbl_create_layered_ex(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,
+                                                int(damped), device, C.byref(h))
         elif osd_order is not None:
             self._gf_mat = np.ascontiguousarray(datafiles.gf_matrices(code.q) if gf_mat is None else gf_mat, dtype=np.uint8)
             self.osd = OsdParams(osd_order, osd_flag, osd_factor, crc_len, crc_rows, self._gf_mat.ctypes.data)

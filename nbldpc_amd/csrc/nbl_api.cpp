@@ -41,7 +41,7 @@ static bool small_enabled()
 // The kernel choice of this decoder as it stands (nbl_plan.cpp): once per workspace check and once per decode, never per launch
 static NblPlan plan_of(const nbl_decoder *d)
 {
-	return nbl_plan(d->shape, d->prm, d->ext, d->layered, d->force_generic, d->record_state, small_enabled(), d->fht, d->ems_wide, d->tems_wide, d->bp_wide, d->fht32);
+	return nbl_plan(d->shape, d->prm, NblPlanReq{d->kind, d->layered, d->force_generic, d->record_state, small_enabled()});
 }
 
 // nbl_create_fht32: the FP64 L_ch every front end fills, the float state the iterations run on, decisions and flags.  The FP64 c2v /
@@ -76,7 +76,7 @@ static nbl_status ensure_workspace32(nbl_decoder *d, int B)
 
 nbl_status widen_state(nbl_decoder *d, hipStream_t reader)
 {
-	if (!d->fht32 || d->last_B <= 0 || !d->w32.c2v) return NBL_OK;
+	if (d->kind != NBL_KIND_FHT32 || d->last_B <= 0 || !d->w32.c2v) return NBL_OK;
 	hipStream_t st = reader ? reader : d->stream;
 	if (d->wide_valid && d->wide_stream == st) return NBL_OK;
 	const size_t q = d->g.q, N = d->g.N, E = d->g.E, cap = (size_t)d->cap;
@@ -98,8 +98,8 @@ nbl_status widen_state(nbl_decoder *d, hipStream_t reader)
 
 nbl_status ensure_workspace(nbl_decoder *d, int B)
 {
-	if (d->fht32) return ensure_workspace32(d, B);
 	const NblPlan plan = plan_of(d);
+	if (plan.f32) return ensure_workspace32(d, B);
 	const bool want_v2c = plan.want_v2c;
 	const bool want_post = d->record_state || d->osd_acc;
 	if (B <= d->cap && (!want_post || d->w.post) && (!want_v2c || d->w.v2c)) return NBL_OK;
@@ -248,75 +248,41 @@ extern "C" nbl_status nbl_last_timing(nbl_decoder *d, double ms[4], int64_t laun
 }
 
 // Diagnostic only (not part of include/nbldpc.h): the kernel choice for a code description -- the shape and the plan, nothing else;
-// no device, no decoder, no field tables.  layered_flags: NBL_LAYERED_* of nbl_create_layered_ex, -1 = the flooding schedule.
+// no device, no decoder, no field tables.
 struct nbl_plan_info { const char *cn; int32_t fusable, fused, want_v2c; };
-extern "C" nbl_status nbl_debug_plan(const nbl_code_desc *code, const nbl_params *params, const nbl_params_ext *ext, int32_t layered_flags,
-                                     int32_t force_generic, int32_t record_state, nbl_plan_info *out)
+static nbl_status plan_info(const nbl_code_desc *code, const nbl_params *params, NblKind kind, bool layered, int32_t force_generic, int32_t record_state,
+                            nbl_plan_info *out)
 {
 	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
-	const NblPlan plan = nbl_plan(nbl_shape(code), *params, ext ? *ext : nbl_params_ext{}, layered_flags >= 0, force_generic, record_state != 0, small_enabled());
-	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
-	return NBL_OK;
-}
-
-// The same for a decoder nbl_create_fht would make; fht_flags: NBL_FHT_* of include/nbldpc.h
-extern "C" nbl_status nbl_debug_plan_fht(const nbl_code_desc *code, const nbl_params *params, uint32_t fht_flags, int32_t force_generic, int32_t record_state,
-                                         nbl_plan_info *out)
-{
-	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
-	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (fht_flags & NBL_FHT_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), true);
-	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
-	return NBL_OK;
-}
-
-// The same for a decoder nbl_create_fht32 would make; fht_flags: NBL_FHT32_* of include/nbldpc.h
-extern "C" nbl_status nbl_debug_plan_fht32(const nbl_code_desc *code, const nbl_params *params, uint32_t fht_flags, int32_t force_generic, int32_t record_state,
-                                           nbl_plan_info *out)
-{
-	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
-	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (fht_flags & NBL_FHT32_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), false, false,
-	                              false, false, true);
+	const NblPlan plan = nbl_plan(nbl_shape(code), *params, NblPlanReq{kind, layered, force_generic, record_state != 0, small_enabled()});
 	*out = {nbl_plan_name(plan), plan.fusable, plan.fused, plan.want_v2c};
 	return NBL_OK;
 }
 
-// The same for a decoder nbl_create_ems_wide would make; wide_flags: NBL_EMS_WIDE_* of include/nbldpc.h
-extern "C" nbl_status nbl_debug_plan_ems_wide(const nbl_code_desc *code, const nbl_params *params, uint32_t wide_flags, int32_t force_generic, int32_t record_state,
-                                              nbl_plan_info *out)
+// The decoder nbl_create* / nbl_create_layered* would make.  layered_flags: NBL_LAYERED_* of nbl_create_layered_ex, -1 = the flooding
+// schedule; ext: as nbl_create_ex takes it (the plan reads nothing of it)
+extern "C" nbl_status nbl_debug_plan(const nbl_code_desc *code, const nbl_params *params, const nbl_params_ext *, int32_t layered_flags,
+                                     int32_t force_generic, int32_t record_state, nbl_plan_info *out)
 {
-	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
-	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (wide_flags & NBL_EMS_WIDE_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), false, true);
-	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
-	return NBL_OK;
+	return plan_info(code, params, NBL_KIND_BASE, layered_flags >= 0, force_generic, record_state, out);
+}
+
+// The decoder the entry point of a kind would make.  kind_name: "fht", "fht32", "ems_wide", "tems_wide" or "bp_wide" (NblEntry::name);
+// layered: nonzero = with the kind's NBL_*_LAYERED flag
+extern "C" nbl_status nbl_debug_plan_kind(const nbl_code_desc *code, const nbl_params *params, const char *kind_name, int32_t layered,
+                                          int32_t force_generic, int32_t record_state, nbl_plan_info *out)
+{
+	const NblEntry *en = nbl_entry_named(kind_name);
+	return en ? plan_info(code, params, en->kind, layered != 0, force_generic, record_state, out) : NBL_ERR_ARG;
 }
 
 // Diagnostic only (not part of include/nbldpc.h): the bytes of LDS one check of an nbl_create_ems_wide decoder takes -- the one function
 // creation's refusal and both launchers use
 extern "C" uint64_t nbl_debug_ems_wide_lds_bytes(int32_t q, int32_t maxdc, int32_t nm, int32_t nc) { return nbl_ems_wide_lds_bytes(q, maxdc, nm, nc); }
 
-// The same for a decoder nbl_create_tems_wide would make; wide_flags: NBL_TEMS_WIDE_* of include/nbldpc.h
-extern "C" nbl_status nbl_debug_plan_tems_wide(const nbl_code_desc *code, const nbl_params *params, uint32_t wide_flags, int32_t force_generic, int32_t record_state,
-                                               nbl_plan_info *out)
-{
-	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
-	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (wide_flags & NBL_TEMS_WIDE_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), false, false, true);
-	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
-	return NBL_OK;
-}
-
 // Diagnostic only (not part of include/nbldpc.h): the bytes of LDS one check of the wide T-EMS programme takes -- the one function
 // creation's refusal and both launchers use
 extern "C" uint64_t nbl_debug_tems_wide_lds_bytes(int32_t q, int32_t maxdc, int32_t nr, int32_t nc) { return nbl_tems_wide_lds_bytes(q, maxdc, nr, nc); }
-
-// The same for a decoder nbl_create_bp_wide would make; wide_flags: NBL_BP_WIDE_* of include/nbldpc.h
-extern "C" nbl_status nbl_debug_plan_bp_wide(const nbl_code_desc *code, const nbl_params *params, uint32_t wide_flags, int32_t force_generic, int32_t record_state,
-                                             nbl_plan_info *out)
-{
-	if (!code || !params || !out || code->N <= 0 || code->M <= 0) return NBL_ERR_ARG;
-	const NblPlan plan = nbl_plan(nbl_shape(code), *params, nbl_params_ext{}, (wide_flags & NBL_BP_WIDE_LAYERED) != 0, force_generic, record_state != 0, small_enabled(), false, false, false, true);
-	*out = {nbl_cn_name(plan.cn), plan.fusable, plan.fused, plan.want_v2c};
-	return NBL_OK;
-}
 
 // Diagnostic only (not part of include/nbldpc.h): the bytes of LDS one check of the wide log-QSPA programme takes -- the one function both
 // launchers size by (below 160 KB for every shape the ABI accepts: creation has nothing to refuse)
@@ -339,11 +305,25 @@ extern "C" uint64_t nbl_debug_tems_wide_path_key(const int32_t *cols, const int3
 // Diagnostic only: the digit of column `col` of a path code, by the kernels' own extraction
 extern "C" int32_t nbl_debug_tems_wide_path_digit(uint64_t code, int32_t col) { return (col < 0 || col > 31) ? -1 : nbl_tems_path_digit(code, col); }
 
+struct LayerRange { int off, cnt; }; // checks ly.chk[off .. off + cnt) : one layer
+
+static bool cn_is_layered(NblCn cn)
+{
+	switch (cn) {
+	case NBL_CN_EMS_LAYERED: case NBL_CN_TEMS_LAYERED: case NBL_CN_BP_LAYERED: case NBL_CN_FHT_LAYERED: case NBL_CN_EMS_WIDE_LAYERED:
+	case NBL_CN_TEMS_WIDE_LAYERED: case NBL_CN_BP_WIDE_LAYERED: case NBL_CN_FHT_WIDE_LAYERED: return true;
+	default: return false;
+	}
+}
+
 // The one launch of check-node kernel `cn`; fused: with the variable-node pass inside (w then carries c2v_prev).  The layered kernels
-// run once per layer and are launched where the layers are walked (enqueue_window).
-static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const NblRun &r, bool fused, hipStream_t st)
+// run once per layer: `lr` names the layer's checks, and is NULL for every other kernel.
+static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const NblRun &r, bool fused, hipStream_t st, const LayerRange *lr = nullptr)
 {
 	const NblGraphDev &g = d->g;
+	const bool f32 = d->kind == NBL_KIND_FHT32; // (NblPlan::f32: fht / fht_layered run by the binary32 instance on the float state)
+	if (cn_is_layered(cn) != (lr != nullptr)) { d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED; }
+	const int off = lr ? lr->off : 0, cnt = lr ? lr->cnt : 0;
 	switch (cn) {
 	case NBL_CN_EMS256: HIP_TRY(d, nbl_launch_cn_ems256(g, w, r, fused, st)); break;
 	case NBL_CN_EMS_SMALL: HIP_TRY(d, nbl_launch_cn_ems_small(g, w, r, fused, st)); break;
@@ -357,15 +337,22 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_BP64: HIP_TRY(d, nbl_launch_cn_bp64(g, w, r, fused, st)); break;
 	case NBL_CN_BP_SMALL: HIP_TRY(d, nbl_launch_cn_bp_small(g, w, r, fused, st)); break;
 	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
-	case NBL_CN_FHT:
-		if (d->fht32) HIP_TRY(d, nbl_launch_cn_fht32(g, w, d->w32, r, st)); // (NblPlan::f32: the binary32 instance on the float state)
-		else HIP_TRY(d, nbl_launch_cn_fht(g, w, r, st));
-		break;
+	case NBL_CN_FHT: HIP_TRY(d, f32 ? nbl_launch_cn_fht32(g, w, d->w32, r, st) : nbl_launch_cn_fht(g, w, r, st)); break;
 	case NBL_CN_FHT_WIDE: HIP_TRY(d, nbl_launch_cn_fht_wide(g, w, r, st)); break;
 	case NBL_CN_EMS_WIDE: HIP_TRY(d, nbl_launch_cn_ems_wide(g, w, r, st)); break;
 	case NBL_CN_TEMS_WIDE: HIP_TRY(d, nbl_launch_cn_tems_wide(g, w, r, st)); break;
 	case NBL_CN_BP_WIDE: HIP_TRY(d, nbl_launch_cn_bp_wide(g, w, r, st)); break;
 	case NBL_CN_BSTEMS: HIP_TRY(d, nbl_launch_cn_bstems(g, w, r, st)); break;
+	case NBL_CN_EMS_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_TEMS_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_BP_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_FHT_LAYERED:
+		HIP_TRY(d, f32 ? nbl_launch_cn_fht32_layered(g, w, d->w32, r, d->ly, off, cnt, st) : nbl_launch_cn_fht_layered(g, w, r, d->ly, off, cnt, st));
+		break;
+	case NBL_CN_EMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_TEMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_BP_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_FHT_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
 	return NBL_OK;
@@ -407,6 +394,20 @@ static bool defers_last(const nbl_decoder *d, const NblPlan &plan)
 	       !d->osd_acc && !d->osd_on && !d->w.post && !d->w.stamps;
 }
 
+// The variable-node pass of the flooding schedule (v2c, posterior, decision), and that of the layered one (posterior and decision from
+// the c2v as it stands); on a binary32 plan the same passes on the float state, the flooding one damped
+static hipError_t launch_vn(const IterCtx &c, hipStream_t st)
+{
+	const nbl_decoder *d = c.d;
+	return c.plan.f32 ? nbl_launch_vn32(d->g, d->w, d->w32, c.r, true, st) : nbl_launch_vn(d->g, d->w, c.r, c.damp, st);
+}
+
+static hipError_t launch_vn_decide(const IterCtx &c, hipStream_t st)
+{
+	const nbl_decoder *d = c.d;
+	return c.plan.f32 ? nbl_launch_vn32(d->g, d->w, d->w32, c.r, false, st) : nbl_launch_vn_decide(d->g, d->w, c.r, st);
+}
+
 // launches of iterations it_lo .. it_hi on `st`
 static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t st, bool count)
 {
@@ -416,29 +417,15 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 		if (d->layered) {
 			// decision and syndrome from the c2v the previous iteration left, then the layers in order, each on the c2v the layers
 			// before it have just written (one buffer; the launches of a stream run in order)
-			if (d->fht32) HIP_TRY(d, nbl_launch_vn32(d->g, d->w, d->w32, c.r, false, st)); // (the same pass on the float state)
-			else HIP_TRY(d, nbl_launch_vn_decide(d->g, d->w, c.r, st));
+			HIP_TRY(d, launch_vn_decide(c, st));
 			HIP_TRY(d, mark(c, 0, st));
 			HIP_TRY(d, nbl_launch_syn(d->g, d->w, c.r, st));
 			HIP_TRY(d, mark(c, 1, st));
 			// (T-EMS, log-QSPA: each check also damps its inputs against the v2c buffer and updates it in place; init_kernel has set
 			// v2c = L_ch)
 			for (int l = 0; l < d->n_layers; l++) {
-				const int off = d->h_lay_off[l], cnt = d->h_lay_off[l + 1] - off;
-				switch (c.plan.cn) {
-				case NBL_CN_EMS_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_TEMS_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_BP_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_FHT_LAYERED:
-					if (d->fht32) HIP_TRY(d, nbl_launch_cn_fht32_layered(d->g, d->w, d->w32, c.r, d->ly, off, cnt, st));
-					else HIP_TRY(d, nbl_launch_cn_fht_layered(d->g, d->w, c.r, d->ly, off, cnt, st));
-					break;
-				case NBL_CN_EMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_TEMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_BP_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				case NBL_CN_FHT_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_wide_layered(d->g, d->w, c.r, d->ly, off, cnt, st)); break;
-				default: d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED;
-				}
+				const LayerRange lr = {d->h_lay_off[l], d->h_lay_off[l + 1] - d->h_lay_off[l]};
+				if (const nbl_status s = launch_cn(d, c.plan.cn, d->w, c.r, false, st, &lr)) return s;
 			}
 			HIP_TRY(d, mark(c, 2, st));
 			if (count) { d->launches[0]++; d->launches[1]++; d->launches[2] += d->n_layers; }
@@ -476,8 +463,7 @@ static nbl_status enqueue_window(IterCtx &c, int it_lo, int it_hi, hipStream_t s
 			if (count) { d->launches[2]++; d->launches[1]++; }
 			continue;
 		}
-		if (d->fht32) HIP_TRY(d, nbl_launch_vn32(d->g, d->w, d->w32, c.r, true, st)); // (the same pass, damped, on the float state)
-		else HIP_TRY(d, nbl_launch_vn(d->g, d->w, c.r, c.damp, st));
+		HIP_TRY(d, launch_vn(c, st));
 		HIP_TRY(d, mark(c, 0, st));
 		if (d->osd_acc) {
 			HIP_TRY(d, nbl_launch_osd_acc(d->w.post, d->ws.osd_S, c.batch, d->g.N, d->g.p, d->g.q, d->osd_factor, it == 1, st));
@@ -560,9 +546,9 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 	HIP_TRY(d, mark(c, 3, st));
 	// (nbl_create_fht32: L_ch and the flags alone -- no FP64 message buffer need exist; then the one narrowing launch of the call, which
 	// also sets the float v2c = Lf and c2v = 0.  Its time is in ms[3] alone: nbl_last_timing has no launch counter for it)
-	HIP_TRY(d, nbl_launch_init(d_Lin, d->g, d->w, B, d->fht32 ? 2 : (c.damp ? 1 : 0) | (c.zeros ? 2 : 0), st)); // bit 1: c2v is not cleared
+	HIP_TRY(d, nbl_launch_init(d_Lin, d->g, d->w, B, c.plan.f32 ? 2 : (c.damp ? 1 : 0) | (c.zeros ? 2 : 0), st)); // bit 1: c2v is not cleared
 	HIP_TRY(d, mark(c, 3, st));
-	if (d->fht32) {
+	if (c.plan.f32) {
 		HIP_TRY(d, nbl_launch_narrow32(d->g, d->w.Lch, d->w32, B, st));
 		HIP_TRY(d, mark(c, 3, st));
 		d->wide_valid = false;

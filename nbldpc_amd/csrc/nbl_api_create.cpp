@@ -247,112 +247,125 @@ struct LayerReq { const int32_t *layer_of; uint32_t flags; bool bp; };
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out,
-                              bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false, bool fht32 = false);
+                              NblKind kind);
 
 extern "C" nbl_status nbl_create_osd(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const nbl_params_ext *ext, const nbl_osd_params *osd, int device, nbl_decoder **out)
 {
-	return create_impl(code, gf_mul, gf_inv, params, ext, osd, nullptr, device, out);
+	return create_impl(code, gf_mul, gf_inv, params, ext, osd, nullptr, device, out, NBL_KIND_BASE);
 }
 
 extern "C" nbl_status nbl_create_layered(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                          const int32_t *layer_of, int device, nbl_decoder **out)
 {
 	const LayerReq lay = {layer_of, 0, false};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out, NBL_KIND_BASE);
 }
 
 extern "C" nbl_status nbl_create_layered_ex(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                             const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
 	const LayerReq lay = {layer_of, flags, false};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out, NBL_KIND_BASE);
 }
 
 extern "C" nbl_status nbl_create_layered_bp(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                             const int32_t *layer_of, int device, nbl_decoder **out)
 {
 	const LayerReq lay = {layer_of, 0, true};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out);
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, &lay, device, out, NBL_KIND_BASE);
 }
 
-// FHT sum-product decoding (include/nbldpc.h): flooding without a LayerReq, layered with the request of nbl_create_layered_bp -- the same
-// assignment rules, the same v2c state
+// The entry points that name a kind (include/nbldpc.h).  Each is flooding without a LayerReq and layered with the request of the
+// nbl_create_layered* function its row names -- the same assignment rules, the same v2c state (EMS: none)
+#define NBL_STR_(x) #x
+#define NBL_STR(x) NBL_STR_(x)
+static constexpr const char *FHT_ONLY = " runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, which no other "
+                                        "method's check node is";
+static const NblEntry nbl_entries[] = {
+	// FHT sum-product decoding.  The wide programme's storage does not grow with the check degree, so its limit is the LDS block's, 32; the
+	// variable side -- the layer rows, the variable-node pass -- keeps 8 everywhere.  Layered: nbl_create_layered_bp
+	{NBL_KIND_FHT, "fht", "nbl_create_fht", NBL_FHT_LAYERED, "NBL_FHT_LAYERED", NBL_METHOD_BP, FHT_ONLY, NBL_FHT_MAX_CHECK_DEGREE, "", 0, true},
+	// The same in single precision: a float message state.  The product of up to 7 transformed vectors and its transform stay inside
+	// binary32's range; no wide layout
+	{NBL_KIND_FHT32, "fht32", "nbl_create_fht32", NBL_FHT32_LAYERED, "NBL_FHT32_LAYERED", NBL_METHOD_BP, FHT_ONLY, NBL_MAXDC,
+	 ": products of more transformed vectors leave the range of single precision; nbl_create_fht (double precision) takes check degrees up to "
+	 NBL_STR(NBL_FHT_MAX_CHECK_DEGREE), 0, true},
+	// EMS, one workgroup per check, no array sized by the degree; the limit is the header's, the LDS bound is checked in create_impl.
+	// Layered: nbl_create_layered
+	{NBL_KIND_EMS_WIDE, "ems_wide", "nbl_create_ems_wide", NBL_EMS_WIDE_LAYERED, "NBL_EMS_WIDE_LAYERED", NBL_METHOD_EMS,
+	 " runs EMS (method 2) only: the other methods keep their entry points and their check-degree limit of 8 (log-QSPA above it: nbl_create_fht)",
+	 NBL_EMS_MAX_CHECK_DEGREE, "", 0, false},
+	// T-EMS over any field, the same shape of programme; its path code holds columns up to 31.  Layered: nbl_create_layered_ex(..,
+	// NBL_LAYERED_DAMPED)
+	{NBL_KIND_TEMS_WIDE, "tems_wide", "nbl_create_tems_wide", NBL_TEMS_WIDE_LAYERED, "NBL_TEMS_WIDE_LAYERED", NBL_METHOD_TEMS,
+	 " runs T-EMS (method 4) only: the other methods keep their entry points (EMS above check degree 8: nbl_create_ems_wide, log-QSPA: nbl_create_fht)",
+	 NBL_TEMS_MAX_CHECK_DEGREE, "", NBL_LAYERED_DAMPED, false},
+	// Exact log-QSPA, the same shape of programme; (maxdc + 5) q 8 + 256 bytes of LDS, at most 76,032 B -- nothing to refuse for LDS.
+	// Layered: nbl_create_layered_bp
+	{NBL_KIND_BP_WIDE, "bp_wide", "nbl_create_bp_wide", NBL_BP_WIDE_LAYERED, "NBL_BP_WIDE_LAYERED", NBL_METHOD_BP,
+	 " runs exact log-QSPA (method 1) only: the other methods keep their entry points (EMS above check degree 8: nbl_create_ems_wide, T-EMS: nbl_create_tems_wide)",
+	 NBL_BP_MAX_CHECK_DEGREE, "", 0, true},
+};
+
+const NblEntry *nbl_entry(NblKind kind)
+{
+	for (const NblEntry &en : nbl_entries)
+		if (en.kind == kind) return &en;
+	return nullptr;
+}
+
+const NblEntry *nbl_entry_named(const char *name)
+{
+	for (const NblEntry &en : nbl_entries)
+		if (name && !strcmp(en.name, name)) return &en;
+	return nullptr;
+}
+
+static nbl_status create_kind(NblKind kind, const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                              const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	const NblEntry &en = *nbl_entry(kind);
+	if (!out) return NBL_ERR_ARG;
+	*out = nullptr;
+	if (flags & ~en.layered_bit)
+		return fail_create(nullptr, NBL_ERR_ARG, std::string(en.fn) + ": unknown flag bit (flags = " + std::to_string(flags) + "; " + en.layered_flag + " = " +
+		                                         std::to_string(en.layered_bit) + " is the only one defined)");
+	if (!(flags & en.layered_bit) && layer_of)
+		return fail_create(nullptr, NBL_ERR_ARG, std::string(en.fn) + ": a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or set " +
+		                                         en.layered_flag + ")");
+	const LayerReq lay = {layer_of, en.lay_flags, en.lay_bp};
+	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & en.layered_bit) ? &lay : nullptr, device, out, kind);
+}
+
 extern "C" nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                      const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
-	if (!out) return NBL_ERR_ARG;
-	*out = nullptr;
-	if (flags & ~(uint32_t)NBL_FHT_LAYERED)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_FHT_LAYERED = 1 is the only one defined)");
-	if (!(flags & NBL_FHT_LAYERED) && layer_of)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or set "
-		                                         "NBL_FHT_LAYERED)");
-	const LayerReq lay = {layer_of, 0, true};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_FHT_LAYERED) ? &lay : nullptr, device, out, true);
+	return create_kind(NBL_KIND_FHT, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
-// Single-precision FHT sum-product decoding (include/nbldpc.h): the requests of nbl_create_fht, a float message state, checks up to degree 8
 extern "C" nbl_status nbl_create_fht32(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                        const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
-	if (!out) return NBL_ERR_ARG;
-	*out = nullptr;
-	if (flags & ~(uint32_t)NBL_FHT32_LAYERED)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht32: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_FHT32_LAYERED = 1 is the only one defined)");
-	if (!(flags & NBL_FHT32_LAYERED) && layer_of)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht32: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or set "
-		                                         "NBL_FHT32_LAYERED)");
-	const LayerReq lay = {layer_of, 0, true};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_FHT32_LAYERED) ? &lay : nullptr, device, out, false, false, false, false, true);
+	return create_kind(NBL_KIND_FHT32, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
-// EMS with check degrees up to NBL_EMS_MAX_CHECK_DEGREE (include/nbldpc.h): flooding without a LayerReq, layered with the request of
-// nbl_create_layered -- the same assignment rules, no v2c state
 extern "C" nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                           const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
-	if (!out) return NBL_ERR_ARG;
-	*out = nullptr;
-	if (flags & ~(uint32_t)NBL_EMS_WIDE_LAYERED)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_EMS_WIDE_LAYERED = 1 is the only one defined)");
-	if (!(flags & NBL_EMS_WIDE_LAYERED) && layer_of)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or "
-		                                         "set NBL_EMS_WIDE_LAYERED)");
-	const LayerReq lay = {layer_of, 0, false};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_EMS_WIDE_LAYERED) ? &lay : nullptr, device, out, false, true);
+	return create_kind(NBL_KIND_EMS_WIDE, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
-// T-EMS with check degrees up to NBL_TEMS_MAX_CHECK_DEGREE over any field (include/nbldpc.h): flooding without a LayerReq, layered with the
-// request of nbl_create_layered_ex(.., NBL_LAYERED_DAMPED) -- the same assignment rules, the same v2c state
 extern "C" nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                            const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
-	if (!out) return NBL_ERR_ARG;
-	*out = nullptr;
-	if (flags & ~(uint32_t)NBL_TEMS_WIDE_LAYERED)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_TEMS_WIDE_LAYERED = 1 is the only one defined)");
-	if (!(flags & NBL_TEMS_WIDE_LAYERED) && layer_of)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or "
-		                                         "set NBL_TEMS_WIDE_LAYERED)");
-	const LayerReq lay = {layer_of, NBL_LAYERED_DAMPED, false};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_TEMS_WIDE_LAYERED) ? &lay : nullptr, device, out, false, false, true);
+	return create_kind(NBL_KIND_TEMS_WIDE, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
-// Exact log-QSPA with check degrees up to NBL_BP_MAX_CHECK_DEGREE (include/nbldpc.h): flooding without a LayerReq, layered with the request
-// of nbl_create_layered_bp -- the same assignment rules, the same v2c state
 extern "C" nbl_status nbl_create_bp_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                                          const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
-	if (!out) return NBL_ERR_ARG;
-	*out = nullptr;
-	if (flags & ~(uint32_t)NBL_BP_WIDE_LAYERED)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_bp_wide: unknown flag bit (flags = " + std::to_string(flags) + "; NBL_BP_WIDE_LAYERED = 1 is the only one defined)");
-	if (!(flags & NBL_BP_WIDE_LAYERED) && layer_of)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_bp_wide: a layer assignment belongs to the layered schedule (flags = 0 is flooding: pass layer_of = NULL, or "
-		                                         "set NBL_BP_WIDE_LAYERED)");
-	const LayerReq lay = {layer_of, 0, true};
-	return create_impl(code, gf_mul, gf_inv, params, nullptr, nullptr, (flags & NBL_BP_WIDE_LAYERED) ? &lay : nullptr, device, out, false, false, false, true);
+	return create_kind(NBL_KIND_BP_WIDE, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
 extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
@@ -364,9 +377,10 @@ extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, in
 }
 
 static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
-                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, bool fht, bool ems_wide,
-                              bool tems_wide, bool bp_wide, bool fht32)
+                              const nbl_params_ext *ext, const nbl_osd_params *osd, const LayerReq *lay, int device, nbl_decoder **out, NblKind kind)
 {
+	const NblEntry *const en = nbl_entry(kind); // NULL: nbl_create* / nbl_create_layered*
+	const bool ems_wide = kind == NBL_KIND_EMS_WIDE, tems_wide = kind == NBL_KIND_TEMS_WIDE;
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
 	if (!code || !gf_mul || !gf_inv || !params) return fail_create(nullptr, NBL_ERR_ARG, "null argument");
@@ -379,21 +393,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	std::string field_err;
 	const int poly = validate_field(q, gf_mul, gf_inv, field_err);
 	if (!poly) return fail_create(nullptr, NBL_ERR_ARG, field_err);
-	if (fht && params->method != NBL_METHOD_BP)
-		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_fht runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, "
-		                                                 "which no other method's check node is");
-	if (fht32 && params->method != NBL_METHOD_BP)
-		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_fht32 runs the sum-product rule of log-QSPA (method 1) only: the transform evaluates its XOR convolution, "
-		                                                 "which no other method's check node is");
-	if (ems_wide && params->method != NBL_METHOD_EMS)
-		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide runs EMS (method 2) only: the other methods keep their entry points and their check-degree "
-		                                                 "limit of 8 (log-QSPA above it: nbl_create_fht)");
-	if (tems_wide && params->method != NBL_METHOD_TEMS)
-		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide runs T-EMS (method 4) only: the other methods keep their entry points (EMS above check "
-		                                                 "degree 8: nbl_create_ems_wide, log-QSPA: nbl_create_fht)");
-	if (bp_wide && params->method != NBL_METHOD_BP)
-		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_bp_wide runs exact log-QSPA (method 1) only: the other methods keep their entry points (EMS above check "
-		                                                 "degree 8: nbl_create_ems_wide, T-EMS: nbl_create_tems_wide)");
+	if (en && params->method != en->method) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, std::string(en->fn) + en->method_text);
 	if (lay && lay->bp && params->method != NBL_METHOD_BP)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_layered_bp runs log-QSPA (method 1) only: the layered schedule of EMS (method 2) is behind "
 		                                                 "nbl_create_layered, that of T-EMS (method 4) behind nbl_create_layered_ex with NBL_LAYERED_DAMPED");
@@ -483,29 +483,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	}
 	const int E = voff[N];
 	if (coff[M] != E) return fail_create(nullptr, NBL_ERR_ARG, "variable-side and check-side edge counts differ");
-	// (nbl_create_fht: the wide programme's storage does not grow with the check degree, so its limit is the LDS block's, 32; the variable
-	// side -- the layer rows, the variable-node pass -- keeps 8 everywhere)
-	if (fht && maxdv <= NBL_MAXDV && maxdc > NBL_FHT_MAX_CHECK_DEGREE)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
-		                                         std::to_string(NBL_FHT_MAX_CHECK_DEGREE) + ")");
-	// (nbl_create_fht32: the product of up to 7 transformed vectors and its transform stay inside binary32's range; no wide layout)
-	if (fht32 && maxdv <= NBL_MAXDV && maxdc > NBL_MAXDC)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_fht32: check degree " + std::to_string(maxdc) + " above the supported maximum (" + std::to_string(NBL_MAXDC) +
-		                                         "): products of more transformed vectors leave the range of single precision; nbl_create_fht (double precision) takes "
-		                                         "check degrees up to " + std::to_string(NBL_FHT_MAX_CHECK_DEGREE));
-	// (nbl_create_ems_wide: one workgroup per check, no array sized by the degree; the limit is the header's, the LDS bound is checked below)
-	if (ems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_EMS_MAX_CHECK_DEGREE)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_ems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
-		                                         std::to_string(NBL_EMS_MAX_CHECK_DEGREE) + ")");
-	// (nbl_create_tems_wide: the same shape of programme; its path code holds columns up to 31)
-	if (tems_wide && maxdv <= NBL_MAXDV && maxdc > NBL_TEMS_MAX_CHECK_DEGREE)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_tems_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
-		                                         std::to_string(NBL_TEMS_MAX_CHECK_DEGREE) + ")");
-	// (nbl_create_bp_wide: the same shape of programme; (maxdc + 5) q 8 + 256 bytes of LDS, at most 76,032 B -- nothing to refuse for LDS)
-	if (bp_wide && maxdv <= NBL_MAXDV && maxdc > NBL_BP_MAX_CHECK_DEGREE)
-		return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_bp_wide: check degree " + std::to_string(maxdc) + " above the supported maximum (" +
-		                                         std::to_string(NBL_BP_MAX_CHECK_DEGREE) + ")");
-	if ((!fht && !ems_wide && !tems_wide && !bp_wide && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
+	// (a kind's own check-degree ceiling, with its own text, where the variable side is in range: that side keeps 8 everywhere)
+	if (en && maxdv <= NBL_MAXDV && maxdc > en->max_dc)
+		return fail_create(nullptr, NBL_ERR_ARG, std::string(en->fn) + ": check degree " + std::to_string(maxdc) + " above the supported maximum (" +
+		                                         std::to_string(en->max_dc) + ")" + en->max_dc_text);
+	if ((kind == NBL_KIND_BASE && maxdc > NBL_MAXDC) || maxdv > NBL_MAXDV) return fail_create(nullptr, NBL_ERR_ARG, "node degree above the supported maximum (8)");
 	static_assert(NBL_LAYER_ROW >= 4 + NBL_MAXDV, "a layer row holds the c2v slots of every edge of a variable");
 	std::vector<int> v_cpos(E, -1), c_epos(E, -1), c_var(E), c_h(E), c_hinv(E);
 	for (int ce = 0; ce < E; ce++) {
@@ -628,11 +610,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		d->h_layer_of = layer_of;
 		d->h_lay_off = lay_off;
 	}
-	d->fht = fht;
-	d->fht32 = fht32;
-	d->ems_wide = ems_wide;
-	d->tems_wide = tems_wide;
-	d->bp_wide = bp_wide;
+	d->kind = kind;
 	d->h_coff = coff; d->h_cvar = c_var; d->h_ch = c_h;
 	d->h_mul.assign(gf_mul, gf_mul + (size_t)q * q);
 	d->d_e2c_map = (int *)d->g.v_cpos;

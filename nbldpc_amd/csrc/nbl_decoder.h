@@ -79,11 +79,7 @@ struct nbl_decoder {
 	// place; EMS keeps no v2c, T-EMS (NBL_LAYERED_DAMPED) and log-QSPA keep the per-edge v2c their damping reads, updated in place by the
 	// edge's check
 	bool layered = false;
-	bool fht = false;         // nbl_create_fht: the FHT sum-product check node in place of the exact one (flooding or layered)
-	bool fht32 = false;       // nbl_create_fht32: the FHT check node, the variable-node pass and the message state in binary32 (flooding or layered)
-	bool ems_wide = false;    // nbl_create_ems_wide: EMS with check degrees up to NBL_EMS_MAX_CHECK_DEGREE (flooding or layered)
-	bool tems_wide = false;   // nbl_create_tems_wide: T-EMS with check degrees up to NBL_TEMS_MAX_CHECK_DEGREE over any field (flooding or layered)
-	bool bp_wide = false;     // nbl_create_bp_wide: exact log-QSPA with check degrees up to NBL_BP_MAX_CHECK_DEGREE (flooding or layered)
+	NblKind kind = NBL_KIND_BASE; // the entry point that made the handle (nbl_plan.h; flooding or layered, whichever kind)
 	int n_layers = 0;
 	std::vector<int> h_layer_of; // [M] the assignment in use
 	std::vector<int> h_lay_off;  // [n_layers + 1] offsets into ly.chk
@@ -209,6 +205,23 @@ static inline int ilog2(int q)
 // what nbl_soft_output and nbl_read_state refuse after a loop of several passes
 inline const char *const NBL_IDD_SUB_TEXT = ": the last decode call was an iterative-demapping loop (passes > 1), the workspace holds the "
                                             "sub-batch of its last pass and not the batch; run an ordinary decode call first";
+
+// nbl_api_create.cpp: one row per entry point beside nbl_create* / nbl_create_layered* -- what its wrapper, create_impl's method and
+// degree checks and nbl_debug_plan_kind need to know of a kind
+struct NblEntry {
+	NblKind kind;
+	const char *name, *fn;    // "fht" (nbl_debug_plan_kind's kind_name), "nbl_create_fht" (as the messages name it)
+	uint32_t layered_bit;     // its one flag, NBL_*_LAYERED ...
+	const char *layered_flag; // ... and that flag's name
+	int method;               // the one method it runs
+	const char *method_text;  // what follows `fn` in the refusal of any other
+	int max_dc;               // the largest check degree it takes
+	const char *max_dc_text;  // what follows "(max_dc)" in the refusal of a larger one
+	uint32_t lay_flags;       // the layered schedule it runs: NBL_LAYERED_* of nbl_create_layered_ex ...
+	bool lay_bp;              // ... or that of nbl_create_layered_bp
+};
+const NblEntry *nbl_entry(NblKind kind);            // NULL for NBL_KIND_BASE
+const NblEntry *nbl_entry_named(const char *name);  // NULL for a name no row has
 
 // nbl_api.cpp
 extern thread_local std::string g_create_error; // what nbl_last_error(NULL) reports

@@ -39,48 +39,57 @@ static const char *const cn_names[NBL_CN_COUNT] = {
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 const char *nbl_plan_name(const NblPlan &plan) { return !plan.f32 ? cn_names[plan.cn] : plan.cn == NBL_CN_FHT_LAYERED ? "fht32_layered" : "fht32"; }
 
-NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht, bool ems_wide, bool tems_wide, bool bp_wide, bool fht32)
+// `fusable` -- which buffers the workspace holds -- of the default plan (the base kind, switch 0) of the same request: what a wide
+// programme selected by switch 3 keeps, so that the workspace does not move with a debug switch
+static bool base_fusable(const NblShape &s, const nbl_params &prm, NblPlanReq rq)
 {
+	rq.kind = NBL_KIND_BASE;
+	rq.force_generic = 0;
+	return nbl_plan(s, prm, rq).fusable;
+}
+
+NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const NblPlanReq &rq)
+{
+	const bool layered = rq.layered, record_state = rq.record_state, small_on = rq.small_on;
+	const int force_generic = rq.force_generic;
 	NblPlan pl{NBL_CN_NONE, false, false, true, false};
-	if (fht32) { // one general kernel per schedule: never fused; both schedules read the float v2c; no debug switch moves it
+	switch (rq.kind) {
+	case NBL_KIND_FHT32: // one general kernel per schedule: never fused; both schedules read the float v2c; no debug switch moves it
 		pl.cn = layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT;
 		pl.f32 = true;
 		return pl;
-	}
-	if (bp_wide && (s.maxdc > NBL_MAXDC || force_generic == 3)) {
+	case NBL_KIND_BP_WIDE:
+		if (s.maxdc <= NBL_MAXDC && force_generic != 3) break;
 		// the workgroup-per-check programme: never fused; both schedules read v2c (flooding: the inputs; layered: the damping).  With
-		// maxdc <= NBL_MAXDC (switch 3) `fusable` stays that of the decoder's default plan (switch 0), so that the workspace does not move
-		// with a debug switch
-		if (s.maxdc <= NBL_MAXDC) pl.fusable = nbl_plan(s, prm, nbl_params_ext{}, layered, 0, record_state, small_on).fusable;
+		// maxdc <= NBL_MAXDC (switch 3) `fusable` stays that of the decoder's default plan (switch 0)
+		if (s.maxdc <= NBL_MAXDC) pl.fusable = base_fusable(s, prm, rq);
 		pl.cn = layered ? NBL_CN_BP_WIDE_LAYERED : NBL_CN_BP_WIDE;
 		return pl;
-	}
-	if (tems_wide && (nbl_tems_needs_wide(s) || (force_generic == 3 && prm.tems_nc <= NBL_TEMS_WIDE_MAX_NC))) {
+	case NBL_KIND_TEMS_WIDE:
+		if (!nbl_tems_needs_wide(s) && !(force_generic == 3 && prm.tems_nc <= NBL_TEMS_WIDE_MAX_NC)) break;
 		// the workgroup-per-check programme: never fused; both schedules read v2c (flooding: the inputs; layered: the damping).  Inside
-		// nbl_create's envelope (switch 3) `fusable` stays that of the decoder's default plan, so that the workspace does not move with a
-		// debug switch
-		if (!nbl_tems_needs_wide(s)) pl.fusable = nbl_plan(s, prm, nbl_params_ext{}, layered, 0, record_state, small_on).fusable;
+		// nbl_create's envelope (switch 3) `fusable` stays that of the decoder's default plan
+		if (!nbl_tems_needs_wide(s)) pl.fusable = base_fusable(s, prm, rq);
 		pl.cn = layered ? NBL_CN_TEMS_WIDE_LAYERED : NBL_CN_TEMS_WIDE;
 		return pl;
-	}
-	if (ems_wide && (s.maxdc > NBL_MAXDC || force_generic == 3)) {
+	case NBL_KIND_EMS_WIDE:
+		if (s.maxdc <= NBL_MAXDC && force_generic != 3) break;
 		// the workgroup-per-check programme: never fused.  Flooding reads the v2c of the variable-node pass; layered forms its inputs from
-		// L_ch and c2v.  With maxdc <= NBL_MAXDC (switch 3) `fusable` -- which buffers the workspace holds -- stays that of the decoder's
-		// default plan (switch 0), so that the workspace does not move with a debug switch
-		if (s.maxdc <= NBL_MAXDC) pl.fusable = nbl_plan(s, prm, nbl_params_ext{}, layered, 0, record_state, small_on).fusable;
+		// L_ch and c2v.  With maxdc <= NBL_MAXDC (switch 3) `fusable` stays that of the decoder's default plan (switch 0)
+		if (s.maxdc <= NBL_MAXDC) pl.fusable = base_fusable(s, prm, rq);
 		pl.cn = layered ? NBL_CN_EMS_WIDE_LAYERED : NBL_CN_EMS_WIDE;
-		pl.fused = false;
 		pl.want_v2c = !layered;
 		return pl;
-	}
-	if (fht) { // one general kernel per schedule and layout: never fused; both schedules read v2c (flooding: the inputs)
+	case NBL_KIND_FHT: { // one general kernel per schedule and layout: never fused; both schedules read v2c (flooding: the inputs)
 		// the register programme holds DCM = NBL_MAXDC transformed inputs per lane; a code with a larger check takes the wide one.
 		// Debug switches 0, 1, 2 move nothing; 3 selects the wide programme at any degree
 		const bool wide = s.maxdc > NBL_MAXDC || force_generic == 3;
 		pl.cn = wide ? (layered ? NBL_CN_FHT_WIDE_LAYERED : NBL_CN_FHT_WIDE) : (layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT);
 		return pl;
 	}
+	case NBL_KIND_BASE: break;
+	}
+	// the base kind, and a wide kind on a code inside nbl_create's envelope
 	if (layered) { // one c2v buffer updated in place: never fused; T-EMS and log-QSPA keep the v2c their damping reads
 		pl.cn = prm.method == NBL_METHOD_TEMS ? NBL_CN_TEMS_LAYERED : prm.method == NBL_METHOD_BP ? NBL_CN_BP_LAYERED : NBL_CN_EMS_LAYERED;
 		pl.want_v2c = prm.method == NBL_METHOD_TEMS || prm.method == NBL_METHOD_BP;

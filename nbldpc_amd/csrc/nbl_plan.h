@@ -26,22 +26,36 @@ struct NblPlan {
 	bool f32;      // nbl_create_fht32: cn (fht or fht_layered) is run by its binary32 instance on the float message state; named fht32 / fht32_layered
 };
 
+// Which entry point made the decoder.  The kinds exclude one another; each non-base kind runs one method (nbl_entries, nbl_decoder.h):
+//   BASE       nbl_create* / nbl_create_layered*: the precedence of nbl_plan.cpp; force_generic 1 = the general kernel, 2 = the
+//              specialised one, neither fused; 3 changes nothing
+//   FHT        nbl_create_fht (method 1): fht / fht_layered; a code with a check above degree NBL_MAXDC runs fht_wide / fht_wide_layered,
+//              and force_generic 3 selects that wide programme at any check degree (so that the two layouts can be compared on the same
+//              inputs); 0, 1, 2 change nothing
+//   FHT32      nbl_create_fht32 (method 1): the check-node kinds fht / fht_layered in binary32 (NblPlan::f32), never fused, with v2c (the
+//              float one); no debug switch moves it
+//   EMS_WIDE   nbl_create_ems_wide (method 2): a code with a check above degree NBL_MAXDC runs ems_wide / ems_wide_layered under every
+//              switch; any other code gets the plan of nbl_create / nbl_create_layered, except that force_generic 3 selects the wide
+//              programme
+//   TEMS_WIDE  nbl_create_tems_wide (method 4): a code with a check above degree NBL_MAXDC or with log2(q) maxdc > 32 (the path does not
+//              fit tems_check_node's 32-bit code) runs tems_wide / tems_wide_layered under every switch; any other code gets the plan of
+//              nbl_create / nbl_create_layered_ex, except that force_generic 3 selects the wide programme where
+//              tems_nc <= NBL_TEMS_WIDE_MAX_NC
+//   BP_WIDE    nbl_create_bp_wide (method 1): a code with a check above degree NBL_MAXDC runs bp_wide / bp_wide_layered under every
+//              switch; any other code gets the plan of nbl_create / nbl_create_layered_bp, except that force_generic 3 selects the wide
+//              programme
+enum NblKind { NBL_KIND_BASE, NBL_KIND_FHT, NBL_KIND_FHT32, NBL_KIND_EMS_WIDE, NBL_KIND_TEMS_WIDE, NBL_KIND_BP_WIDE };
+
+struct NblPlanReq {
+	NblKind kind;
+	bool layered;      // which of the kind's two schedules
+	int force_generic; // nbl_debug_force_generic's value
+	bool record_state; // nbl_set_record_state's
+	bool small_on;     // the kernels NBL_NO_SMALL switches off (EMS-small, T-EMS-small, BP-small, EMS-64) may be chosen
+};
+
 NblShape nbl_shape(const nbl_code_desc *code);
-// force_generic: nbl_debug_force_generic's value (1 = the general kernel, 2 = the specialised one, neither fused);
-// small_on: the kernels NBL_NO_SMALL switches off (EMS-small, T-EMS-small, BP-small, EMS-64) may be chosen;
-// fht: an nbl_create_fht decoder (method 1; `layered` says which of its two schedules); there force_generic 3 selects the wide
-// programme at any check degree (so that the two layouts can be compared on the same inputs) and 0, 1, 2 change nothing;
-// ems_wide: an nbl_create_ems_wide decoder (method 2): a code with a check above degree NBL_MAXDC runs ems_wide / ems_wide_layered under
-// every switch; any other code gets the plan of nbl_create / nbl_create_layered, except that force_generic 3 selects the wide programme;
-// tems_wide: an nbl_create_tems_wide decoder (method 4): a code with a check above degree NBL_MAXDC or with log2(q) maxdc > 32 (the path
-// does not fit tems_check_node's 32-bit code) runs tems_wide / tems_wide_layered under every switch; any other code gets the plan of
-// nbl_create / nbl_create_layered_ex, except that force_generic 3 selects the wide programme where tems_nc <= NBL_TEMS_WIDE_MAX_NC;
-// bp_wide: an nbl_create_bp_wide decoder (method 1): a code with a check above degree NBL_MAXDC runs bp_wide / bp_wide_layered under
-// every switch; any other code gets the plan of nbl_create / nbl_create_layered_bp, except that force_generic 3 selects the wide programme;
-// fht32: an nbl_create_fht32 decoder (method 1; `layered` says which of its two schedules): the check-node kinds fht / fht_layered in
-// binary32 (NblPlan::f32), never fused, with v2c (the float one); no debug switch moves it
-NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const nbl_params_ext &ext, bool layered, int force_generic, bool record_state,
-                 bool small_on, bool fht = false, bool ems_wide = false, bool tems_wide = false, bool bp_wide = false, bool fht32 = false);
+NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const NblPlanReq &rq);
 // the codes only the wide T-EMS programme runs (creation refuses tems_nc > NBL_TEMS_WIDE_MAX_NC there)
 inline bool nbl_tems_needs_wide(const NblShape &s) { return s.maxdc > NBL_MAXDC || s.p * s.maxdc > 32; }
 const char *nbl_cn_name(NblCn cn);

@@ -114,7 +114,9 @@ def degree9_code():
 
 def test_library_exports_nbl_create_fht32():
     # (not in nb.EXPORTS: tests/test_abi.py holds that list equal to the names its pattern finds in the header, and the pattern stops at a digit)
-    assert hasattr(nb.load_library(), "nbl_create_fht32") and hasattr(nb.load_library(), "nbl_debug_plan_fht32")
+    assert hasattr(nb.load_library(), "nbl_create_fht32")
+    ring = _ring_code(16, 12, 8)                         # the plan query knows the kind by its name, under both schedules
+    assert debug_plan(ring, nb.METHOD_BP, fht32=True)[0] == "fht32" and debug_plan(ring, nb.METHOD_BP, fht32=True, layers="greedy")[0] == "fht32_layered"
     assert nb.FHT32_LAYERED == 1 and nb.load_library().nbl_abi_version() == 1
 
 
