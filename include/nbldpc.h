@@ -313,7 +313,8 @@ nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, con
  *      x * log2(e) does not for |x| above about 8, where the product's rounding alone is |x| 2^-24 relative).
  *   5. Limits.  Check degrees 2 .. 8, variable degrees 1 .. 8: |U[y]| <= q, so a product of up to 7 transformed vectors stays below 2^56
  *      and its transform below 2^64; at degree 32 it would leave binary32's range.  A larger check is NBL_ERR_ARG (the message names
- *      nbl_create_fht32, the degree found and 8, and points to nbl_create_fht).  Any method but 1 is NBL_ERR_UNSUPPORTED (the message names
+ *      nbl_create_fht32, the degree found and 8, and points to nbl_create_fht; nbl_create_fht32_wide, below, takes such a code in single
+ *      precision).  Any method but 1 is NBL_ERR_UNSUPPORTED (the message names
  *      method 1); an unknown flag bit is NBL_ERR_ARG; a non-NULL layer_of with flags 0 is NBL_ERR_ARG; every assignment error of
  *      nbl_create_layered keeps its status and text; everything else nbl_create refuses is refused the same way.  No OSD, no extension
  *      parameters.  All of it before the device is touched.
@@ -335,6 +336,40 @@ nbl_status nbl_create_fht(const nbl_code_desc *code, const uint16_t *gf_mul, con
 nbl_status nbl_create_fht32(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                             const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 
+/* ---- Single-precision FHT decoding for high-rate codes: check degrees up to 32, flooding and layered -----------------------------------
+ * nbl_create_fht32_wide: NBL_METHOD_BP only (no OSD, no extension parameters).  nbl_create_fht32 itself does not change: it keeps its
+ * limit of 8, its refusal text and its plan.  Everything in the statement above holds here (items 1-8: float channel vectors narrowed
+ * once, all arithmetic in binary32 with no contraction, the floor at 2^-16, exp / log within 2 ulp, the exact widening in
+ * nbl_read_state, soft output, every decode entry point).  A code whose checks all have degree 8 or less gets exactly the decoder
+ * nbl_create_fht32 would make.  A code with a check above degree 8 runs the wide programme, whose check-node update has one more step
+ * (tests/fht32_wide_ref.py restates it in numpy):
+ *   3a. Let e_d be the integer with 2^e_d <= U_d[0] < 2^(e_d+1).  (U_d[0] = sum_y u_d[y] >= 1, because one u is exactly 1 and none is
+ *       negative; U_d[0] <= q.)  U_d <- U_d * 2^(-e_d), every slot: a multiplication by a power of two.  Steps 4-7 run on the scaled
+ *       vectors, unchanged.
+ *   Range.  Unscaled, |U[y]| <= q: a product of 31 transformed vectors can reach q^31 = 2^248 at GF(256), and a flat input -- the
+ *   all-zero channel vector of a punctured symbol -- makes U_d[0] = q exactly, so at degree 32 the overflow is the ordinary case.  Scaled,
+ *   |U[y]| < 2, every product stays below 2^31, every transform below 2^39, and t >= V_d[0] >= 1 (the largest of v_d is at least their
+ *   mean, V_d[0], a product of values in [1, 2)).
+ *   Exactness.  Scaling by a power of two is exact unless a value is subnormal.  Every later operation is a product, a sum, or a maximum
+ *   followed by a difference of logs, so the scale cancels in step 7 and the floor of step 6 is relative to the vector's own largest: a
+ *   scaled and an unscaled evaluation of one check differ only in how log rounds a scaled argument in step 7.  The two programmes are
+ *   therefore NOT bit-identical on a code both run; each carries the parity statement of item 8 against its own restatement (16 x the
+ *   case's recorded deviation between the two evaluations of exp / log; tests/fht32_wide_ref.py records D32W per case).
+ *   Noise.  The largest |v32 - v80| / t measured on the CPU at degree 32 is 2^-19.56 (q = 256), about 3.5 bits below the floor; the tests
+ *   hold every case they run to 2^-18.
+ *   flags 0 = flooding (a non-NULL layer_of is NBL_ERR_ARG); NBL_FHT32_WIDE_LAYERED = layered, layer_of == NULL selects the greedy
+ *   assignment; an unknown flag bit is NBL_ERR_ARG.  Limits: check degrees 2 .. 32 (NBL_FHT32_MAX_CHECK_DEGREE; a larger check is
+ *   NBL_ERR_ARG, the message names this entry point, the degree found and 32); variable degrees stay 1 .. 8, with nbl_create's text.  Any
+ *   other method is NBL_ERR_UNSUPPORTED (the message names method 1); every assignment error of nbl_create_layered keeps its status and
+ *   text; everything else nbl_create refuses is refused the same way; all of it before the device is touched.  No shape is refused for
+ *   its LDS (maxdc q 4 bytes, at most 32 KB, at q = 256 and degree 32).
+ *   Every other entry point but nbl_create_fht, nbl_create_ems_wide, nbl_create_tems_wide and nbl_create_bp_wide keeps its check-degree
+ *   limit of 8. */
+#define NBL_FHT32_MAX_CHECK_DEGREE 32
+#define NBL_FHT32_WIDE_LAYERED 1u
+nbl_status nbl_create_fht32_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                 const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
 /* ---- EMS decoding for high-rate codes: check degrees up to 32, flooding and layered ------------------------------------------------
  * nbl_create_ems_wide: NBL_METHOD_EMS only (no OSD, no extension parameters).  There is no new arithmetic: a check's output is the
  * canonical, residue-free EMS value defined above (the maximum over conf(q,1) U conf(nm,nc) of the left-to-right sums over the other
@@ -353,7 +388,8 @@ nbl_status nbl_create_fht32(const nbl_code_desc *code, const uint16_t *gf_mul, c
  *   point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the
  *   active list, the transmitter, channel and error count work unchanged on such a decoder.  nbl_read_state returns post and c2v as on the
  *   corresponding EMS decoder (a non-NULL v2c is refused on the layered kind, as there); nbl_get_layers works on the layered kind.
- *   Every other entry point but nbl_create_fht, nbl_create_tems_wide and nbl_create_bp_wide keeps its check-degree limit of 8. */
+ *   Every other entry point but nbl_create_fht, nbl_create_fht32_wide, nbl_create_tems_wide and nbl_create_bp_wide keeps its check-degree limit
+ *   of 8. */
 #define NBL_EMS_MAX_CHECK_DEGREE 32
 #define NBL_EMS_WIDE_LAYERED 1u
 nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
@@ -380,7 +416,8 @@ nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul
  *   samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and the active list, the transmitter,
  *   channel and error count work unchanged on such a decoder.  nbl_read_state returns post, c2v and v2c as on the corresponding T-EMS
  *   decoder; nbl_get_layers works on the layered kind.
- *   Every other entry point but nbl_create_fht, nbl_create_ems_wide and nbl_create_bp_wide keeps its check-degree limit of 8. */
+ *   Every other entry point but nbl_create_fht, nbl_create_fht32_wide, nbl_create_ems_wide and nbl_create_bp_wide keeps its check-degree limit
+ *   of 8. */
 #define NBL_TEMS_MAX_CHECK_DEGREE 32
 #define NBL_TEMS_WIDE_LAYERED 1u
 nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
@@ -405,7 +442,8 @@ nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mu
  *   entry point (host, device, bits, samples, prior, csi, idd, resident), soft output (plain and extrinsic), fixed_iters, poll_every and
  *   the active list, the transmitter, channel and error count work unchanged on such a decoder.  nbl_read_state returns post, c2v and v2c
  *   as on the corresponding log-QSPA decoder; nbl_get_layers works on the layered kind.
- *   Every other entry point but nbl_create_fht, nbl_create_ems_wide and nbl_create_tems_wide keeps its check-degree limit of 8. */
+ *   Every other entry point but nbl_create_fht, nbl_create_fht32_wide, nbl_create_ems_wide and nbl_create_tems_wide keeps its check-degree limit
+ *   of 8. */
 #define NBL_BP_MAX_CHECK_DEGREE 32
 #define NBL_BP_WIDE_LAYERED 1u
 nbl_status nbl_create_bp_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,

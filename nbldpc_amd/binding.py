@@ -19,11 +19,13 @@ SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
 SOFT_EXTRINSIC = 1
 FHT_LAYERED = 1          # NBL_FHT_LAYERED
 FHT32_LAYERED = 1        # NBL_FHT32_LAYERED
+FHT32_WIDE_LAYERED = 1   # NBL_FHT32_WIDE_LAYERED
 EMS_WIDE_LAYERED = 1     # NBL_EMS_WIDE_LAYERED
 TEMS_WIDE_LAYERED = 1    # NBL_TEMS_WIDE_LAYERED
 BP_WIDE_LAYERED = 1      # NBL_BP_WIDE_LAYERED
 # the entry points that name a decoder kind: the library's name of the kind -> (creation function, its layered flag)
-KIND_ENTRY = {"fht": ("nbl_create_fht", FHT_LAYERED), "fht32": ("nbl_create_fht32", FHT32_LAYERED), "ems_wide": ("nbl_create_ems_wide", EMS_WIDE_LAYERED),
+KIND_ENTRY = {"fht": ("nbl_create_fht", FHT_LAYERED), "fht32": ("nbl_create_fht32", FHT32_LAYERED), "fht32_wide": ("nbl_create_fht32_wide", FHT32_WIDE_LAYERED),
+              "ems_wide": ("nbl_create_ems_wide", EMS_WIDE_LAYERED),
               "tems_wide": ("nbl_create_tems_wide", TEMS_WIDE_LAYERED), "bp_wide": ("nbl_create_bp_wide", BP_WIDE_LAYERED)}
 FADING_NONE, FADING_RAYLEIGH = 0, 1
 
@@ -199,18 +201,19 @@ class PlanInfo(C.Structure):
 
 
 def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=None, bs_nc=2, layers=None, damped=None,
-               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False):
+               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False, fht32_wide=False):
     """The check-node kernel a decoder of this description would run (nbl_debug_plan; host arithmetic, no device, no decoder):
     (kernel name, fusable, fused, want_v2c).  The description is built the way Decoder builds it; layers / damped / fht as there
     (None = flooding), force_generic as nbl_debug_force_generic takes it (with fht, 3 names the wide programme, fht_wide /
     fht_wide_layered, at any check degree; with wide, the decoder nbl_create_ems_wide would make: 3 names ems_wide / ems_wide_layered at
     any check degree; with tems_wide, the decoder nbl_create_tems_wide would make: 3 names tems_wide / tems_wide_layered at any check
     degree where tems_nc <= 4; with bp_wide, the decoder nbl_create_bp_wide would make: 3 names bp_wide / bp_wide_layered at any check
-    degree; with fht32, the decoder nbl_create_fht32 would make: fht32 / fht32_layered under every switch), record_state as
-    nbl_set_record_state.  fht, wide, tems_wide, bp_wide and fht32 exclude one another."""
-    kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32).items() if on]
+    degree; with fht32, the decoder nbl_create_fht32 would make: fht32 / fht32_layered under every switch; with fht32_wide, the decoder
+    nbl_create_fht32_wide would make: 3 names fht32_wide / fht32_wide_layered at any check degree), record_state as
+    nbl_set_record_state.  fht, wide, tems_wide, bp_wide, fht32 and fht32_wide exclude one another."""
+    kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32, fht32_wide=fht32_wide).items() if on]
     if len(kinds) > 1:
-        raise ValueError("fht, wide, tems_wide, bp_wide and fht32 name five different entry points: give one of them")
+        raise ValueError("fht, wide, tems_wide, bp_wide, fht32 and fht32_wide name six different entry points: give one of them")
     lib = load_library()
     params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
     ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
@@ -254,12 +257,15 @@ class Decoder:
     nbl_create_layered_bp (layers="greedy" or an assignment) with check degrees up to NBL_BP_MAX_CHECK_DEGREE = 32.  fht32=True (method 1
     only; without fht, bp, damped, wide, tems_wide, bp_wide, OSD or extension parameters): nbl_create_fht32, the FHT decoder in single
     precision -- float messages, the floor at 2^-16, check degrees up to 8 -- flooding without layers, layered with layers="greedy" or an
-    assignment; read_state and soft_output return doubles that are the exact widening of the float state."""
+    assignment; read_state and soft_output return doubles that are the exact widening of the float state.  fht32_wide=True (method 1
+    only; without any of the other kind flags, bp, damped, OSD or extension parameters): nbl_create_fht32_wide, the same decoder with check
+    degrees up to NBL_FHT32_MAX_CHECK_DEGREE = 32 (a code with a check above degree 8 runs the update with every transformed input scaled
+    by a power of two)."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False):
+                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False, fht32_wide=False):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -290,6 +296,9 @@ class Decoder:
         if fht32 and (fht or bp or damped is not None or wide or tems_wide or bp_wide or osd_order is not None or bs_nm is not None):
             raise ValueError("fht32: nbl_create_fht32 takes no fht / bp / damped / wide / tems_wide / bp_wide flag and neither OSD nor extension parameters "
                              "(layers alone picks its schedule)")
+        if fht32_wide and (fht32 or fht or bp or damped is not None or wide or tems_wide or bp_wide or osd_order is not None or bs_nm is not None):
+            raise ValueError("fht32_wide: nbl_create_fht32_wide takes no fht32 / fht / bp / damped / wide / tems_wide / bp_wide flag and neither OSD nor extension "
+                             "parameters (layers alone picks its schedule)")
         lay = None
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
@@ -299,7 +308,7 @@ class Decoder:
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
             lay = None if self._layer_of is None else self._layer_of.ctypes.data
         # (at most one of the kinds: every pair is refused above)
-        kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32).items() if on]
+        kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32, fht32_wide=fht32_wide).items() if on]
         if kinds:
             fn, layered_flag = KIND_ENTRY[kinds[0]]
             rc = getattr(self.lib, fn)(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,

@@ -44,7 +44,7 @@ static NblPlan plan_of(const nbl_decoder *d)
 	return nbl_plan(d->shape, d->prm, NblPlanReq{d->kind, d->layered, d->force_generic, d->record_state, small_enabled()});
 }
 
-// nbl_create_fht32: the FP64 L_ch every front end fills, the float state the iterations run on, decisions and flags.  The FP64 c2v /
+// nbl_create_fht32 / nbl_create_fht32_wide: the FP64 L_ch every front end fills, the float state the iterations run on, decisions and flags.  The FP64 c2v /
 // v2c / post are not made here (widen_state makes them for the first FP64 reader of the state).
 static nbl_status ensure_workspace32(nbl_decoder *d, int B)
 {
@@ -76,7 +76,7 @@ static nbl_status ensure_workspace32(nbl_decoder *d, int B)
 
 nbl_status widen_state(nbl_decoder *d, hipStream_t reader)
 {
-	if (d->kind != NBL_KIND_FHT32 || d->last_B <= 0 || !d->w32.c2v) return NBL_OK;
+	if (!nbl_kind_f32(d->kind) || d->last_B <= 0 || !d->w32.c2v) return NBL_OK;
 	hipStream_t st = reader ? reader : d->stream;
 	if (d->wide_valid && d->wide_stream == st) return NBL_OK;
 	const size_t q = d->g.q, N = d->g.N, E = d->g.E, cap = (size_t)d->cap;
@@ -180,7 +180,8 @@ extern "C" nbl_status nbl_set_profiling(nbl_decoder *d, int32_t on)
 // Diagnostic only (not part of include/nbldpc.h): route every shape through the generic kernels (1), the specialised ones without the
 // fused iteration (2); on an nbl_create_fht decoder 3 selects the wide programme (nbl_cn_fht_wide.hip) at any check degree, on an
 // nbl_create_ems_wide decoder the workgroup-per-check programme (nbl_cn_ems_wide.hip), on an nbl_create_tems_wide decoder with
-// tems_nc <= NBL_TEMS_WIDE_MAX_NC that of nbl_cn_tems_wide.hip, on an nbl_create_bp_wide decoder that of nbl_cn_bp_wide.hip.
+// tems_nc <= NBL_TEMS_WIDE_MAX_NC that of nbl_cn_tems_wide.hip, on an nbl_create_bp_wide decoder that of nbl_cn_bp_wide.hip, on an
+// nbl_create_fht32_wide decoder that of nbl_cn_fht32_wide.hip.
 extern "C" nbl_status nbl_debug_force_generic(nbl_decoder *d, int32_t on)
 {
 	if (!d) return NBL_ERR_ARG;
@@ -267,7 +268,7 @@ extern "C" nbl_status nbl_debug_plan(const nbl_code_desc *code, const nbl_params
 	return plan_info(code, params, NBL_KIND_BASE, layered_flags >= 0, force_generic, record_state, out);
 }
 
-// The decoder the entry point of a kind would make.  kind_name: "fht", "fht32", "ems_wide", "tems_wide" or "bp_wide" (NblEntry::name);
+// The decoder the entry point of a kind would make.  kind_name: "fht", "fht32", "fht32_wide", "ems_wide", "tems_wide" or "bp_wide" (NblEntry::name);
 // layered: nonzero = with the kind's NBL_*_LAYERED flag
 extern "C" nbl_status nbl_debug_plan_kind(const nbl_code_desc *code, const nbl_params *params, const char *kind_name, int32_t layered,
                                           int32_t force_generic, int32_t record_state, nbl_plan_info *out)
@@ -321,7 +322,7 @@ static bool cn_is_layered(NblCn cn)
 static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const NblRun &r, bool fused, hipStream_t st, const LayerRange *lr = nullptr)
 {
 	const NblGraphDev &g = d->g;
-	const bool f32 = d->kind == NBL_KIND_FHT32; // (NblPlan::f32: fht / fht_layered run by the binary32 instance on the float state)
+	const bool f32 = nbl_kind_f32(d->kind); // (NblPlan::f32: the FHT kinds run by their binary32 instances on the float state)
 	if (cn_is_layered(cn) != (lr != nullptr)) { d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED; }
 	const int off = lr ? lr->off : 0, cnt = lr ? lr->cnt : 0;
 	switch (cn) {
@@ -338,7 +339,7 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_BP_SMALL: HIP_TRY(d, nbl_launch_cn_bp_small(g, w, r, fused, st)); break;
 	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
 	case NBL_CN_FHT: HIP_TRY(d, f32 ? nbl_launch_cn_fht32(g, w, d->w32, r, st) : nbl_launch_cn_fht(g, w, r, st)); break;
-	case NBL_CN_FHT_WIDE: HIP_TRY(d, nbl_launch_cn_fht_wide(g, w, r, st)); break;
+	case NBL_CN_FHT_WIDE: HIP_TRY(d, f32 ? nbl_launch_cn_fht32_wide(g, w, d->w32, r, st) : nbl_launch_cn_fht_wide(g, w, r, st)); break;
 	case NBL_CN_EMS_WIDE: HIP_TRY(d, nbl_launch_cn_ems_wide(g, w, r, st)); break;
 	case NBL_CN_TEMS_WIDE: HIP_TRY(d, nbl_launch_cn_tems_wide(g, w, r, st)); break;
 	case NBL_CN_BP_WIDE: HIP_TRY(d, nbl_launch_cn_bp_wide(g, w, r, st)); break;
@@ -352,7 +353,9 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_EMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
 	case NBL_CN_TEMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
 	case NBL_CN_BP_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
-	case NBL_CN_FHT_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_fht_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_FHT_WIDE_LAYERED:
+		HIP_TRY(d, f32 ? nbl_launch_cn_fht32_wide_layered(g, w, d->w32, r, d->ly, off, cnt, st) : nbl_launch_cn_fht_wide_layered(g, w, r, d->ly, off, cnt, st));
+		break;
 	default: d->err = "check-node kernel for this method is not built yet"; return NBL_ERR_UNSUPPORTED;
 	}
 	return NBL_OK;

@@ -291,6 +291,10 @@ static const NblEntry nbl_entries[] = {
 	{NBL_KIND_FHT32, "fht32", "nbl_create_fht32", NBL_FHT32_LAYERED, "NBL_FHT32_LAYERED", NBL_METHOD_BP, FHT_ONLY, NBL_MAXDC,
 	 ": products of more transformed vectors leave the range of single precision; nbl_create_fht (double precision) takes check degrees up to "
 	 NBL_STR(NBL_FHT_MAX_CHECK_DEGREE), 0, true},
+	// Single precision above degree 8: every transformed input is scaled by a power of two (step 3a), which keeps the products in range; the
+	// wide layout's limit is the LDS block's, 32.  maxdc q 4 bytes, at most 32 KB -- nothing to refuse for LDS.  Layered: nbl_create_layered_bp
+	{NBL_KIND_FHT32_WIDE, "fht32_wide", "nbl_create_fht32_wide", NBL_FHT32_WIDE_LAYERED, "NBL_FHT32_WIDE_LAYERED", NBL_METHOD_BP, FHT_ONLY,
+	 NBL_FHT32_MAX_CHECK_DEGREE, "", 0, true},
 	// EMS, one workgroup per check, no array sized by the degree; the limit is the header's, the LDS bound is checked in create_impl.
 	// Layered: nbl_create_layered
 	{NBL_KIND_EMS_WIDE, "ems_wide", "nbl_create_ems_wide", NBL_EMS_WIDE_LAYERED, "NBL_EMS_WIDE_LAYERED", NBL_METHOD_EMS,
@@ -348,6 +352,12 @@ extern "C" nbl_status nbl_create_fht32(const nbl_code_desc *code, const uint16_t
                                        const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
 {
 	return create_kind(NBL_KIND_FHT32, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
+}
+
+extern "C" nbl_status nbl_create_fht32_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                            const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	return create_kind(NBL_KIND_FHT32_WIDE, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
 extern "C" nbl_status nbl_create_ems_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
@@ -541,7 +551,8 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		// nbl_create_bp_wide accepts -- nothing to refuse; above degree 8 nbl_create_bp_wide runs the workgroup-per-check programme alone,
 		// (maxdc + 5) q 8 + 256 bytes, at most 76,032 B at q = 256 and degree 32 (nbl_bp_wide_lds_bytes), which its launchers opt in for --
 		// nothing to refuse either; FHT: maxdc q 8 bytes, at most
-		// 65,536 B at q = 256 and degree 32, what a launch gets without opting in -- nothing to refuse either)
+		// 65,536 B at q = 256 and degree 32, what a launch gets without opting in -- nothing to refuse either; in single precision
+		// maxdc q 4 bytes, half of that)
 		if (params->method == NBL_METHOD_TEMS) {
 			if (!tems_needs_wide && nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");

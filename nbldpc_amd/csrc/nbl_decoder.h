@@ -42,7 +42,7 @@ struct nbl_decoder {
 		DevBuf<double> osd_S;    // [cap][N p]
 		DevBuf<int> active;      // [cap] active list (early exit, batches of NBL_COMPACT_MIN codewords or more)
 		DevBuf<double> Lin;      // staging of the host-layout input [cap][N][q-1], made by the first nbl_decode_batch: not counted
-		// nbl_create_fht32: the float state the iterations run on (post32 only when state recording is on).  On such a decoder v2c, c2v
+		// nbl_create_fht32 / nbl_create_fht32_wide: the float state the iterations run on (post32 only when state recording is on).  On such a decoder v2c, c2v
 		// and post above are made by the first call that reads the state in FP64 (widen_state), not with the workspace
 		DevBuf<float> Lf, v2c32, c2v32, post32;
 		size_t bytes() const
@@ -51,7 +51,7 @@ struct nbl_decoder {
 			       c2v_zero.size + osd_S.size + active.size + Lf.size + v2c32.size + c2v32.size + post32.size;
 		}
 	} ws;
-	NblWork32 w32{};            // the float launchers' view of the workspace (nbl_create_fht32 only)
+	NblWork32 w32{};            // the float launchers' view of the workspace (nbl_kind_f32 decoders only)
 	bool wide_valid = false;    // w.c2v / w.v2c / w.post hold the widening of the last decode's float state ...
 	hipStream_t wide_stream = nullptr; // ... made on this stream
 	hipStream_t stream = nullptr;
@@ -230,7 +230,7 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 // Runs the deferred check-node pass of the last decode, if one is pending, on d->stream; every reader of the last c2v calls it first.
 // reader: the stream that will read the c2v (NULL or d->stream: nothing more to order).
 nbl_status finish_pending(nbl_decoder *d, hipStream_t reader = nullptr);
-// nbl_create_fht32 decoders (nothing to do on any other): the float post / c2v / v2c of the last decode call widened, exactly, into the
+// nbl_create_fht32 / nbl_create_fht32_wide decoders (nothing to do on any other): the float post / c2v / v2c of the last decode call widened, exactly, into the
 // FP64 w.post / w.c2v / w.v2c, which are made here the first time; every FP64 reader of the message state calls it first.  reader: the
 // stream that will read (NULL: d->stream); the widening runs on it.
 nbl_status widen_state(nbl_decoder *d, hipStream_t reader = nullptr);

@@ -53,6 +53,12 @@ hipError_t nbl_launch_cn_fht_wide_layered(const NblGraphDev &g, const NblWork &w
 hipError_t nbl_launch_cn_fht32(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_fht32_layered(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, const NblLayerDev &ly, int offset, int count,
                                        hipStream_t st);
+// the same with step 3a (every transformed input scaled by a power of two: nbl_cn_fht32_wide_core.h) in the degree-independent layout
+// (nbl_cn_fht32_wide.hip; nbl_create_fht32_wide), checks up to degree NBL_FHT32_MAX_CHECK_DEGREE.  LDS: maxdc q 4 bytes, at most 32 KB; the
+// check's float c2v region holds its forward products until the final store
+hipError_t nbl_launch_cn_fht32_wide(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_fht32_wide_layered(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, const NblLayerDev &ly, int offset, int count,
+                                            hipStream_t st);
 hipError_t nbl_launch_narrow32(const NblGraphDev &g, const double *d_Lch, const NblWork32 &f, int B, hipStream_t st);
 hipError_t nbl_launch_vn32(const NblGraphDev &g, const NblWork &w, const NblWork32 &f, const NblRun &r, bool write_v2c, hipStream_t st);
 hipError_t nbl_launch_widen32(const float *src, double *dst, long long n, hipStream_t st);

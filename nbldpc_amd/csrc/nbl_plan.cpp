@@ -37,7 +37,16 @@ static const char *const cn_names[NBL_CN_COUNT] = {
 	"tems_wide", "tems_wide_layered", "bp_wide", "bp_wide_layered"};
 
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
-const char *nbl_plan_name(const NblPlan &plan) { return !plan.f32 ? cn_names[plan.cn] : plan.cn == NBL_CN_FHT_LAYERED ? "fht32_layered" : "fht32"; }
+const char *nbl_plan_name(const NblPlan &plan)
+{
+	if (!plan.f32) return cn_names[plan.cn];
+	switch (plan.cn) {
+	case NBL_CN_FHT_LAYERED: return "fht32_layered";
+	case NBL_CN_FHT_WIDE: return "fht32_wide";
+	case NBL_CN_FHT_WIDE_LAYERED: return "fht32_wide_layered";
+	default: return "fht32";
+	}
+}
 
 // `fusable` -- which buffers the workspace holds -- of the default plan (the base kind, switch 0) of the same request: what a wide
 // programme selected by switch 3 keeps, so that the workspace does not move with a debug switch
@@ -54,6 +63,15 @@ NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const NblPlanReq &rq)
 	const int force_generic = rq.force_generic;
 	NblPlan pl{NBL_CN_NONE, false, false, true, false};
 	switch (rq.kind) {
+	case NBL_KIND_FHT32_WIDE:
+		// the scaled programme in the degree-independent layout: a code with a larger check than the register programme holds, or
+		// switch 3 at any degree; never fused; both schedules read the float v2c.  Any other request: the plan of NBL_KIND_FHT32
+		if (s.maxdc > NBL_MAXDC || force_generic == 3) {
+			pl.cn = layered ? NBL_CN_FHT_WIDE_LAYERED : NBL_CN_FHT_WIDE;
+			pl.f32 = true;
+			return pl;
+		}
+		[[fallthrough]];
 	case NBL_KIND_FHT32: // one general kernel per schedule: never fused; both schedules read the float v2c; no debug switch moves it
 		pl.cn = layered ? NBL_CN_FHT_LAYERED : NBL_CN_FHT;
 		pl.f32 = true;

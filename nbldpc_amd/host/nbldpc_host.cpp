@@ -179,7 +179,22 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
+	// NBL_FHT32_WIDE=1 (with NBL_BP_CHECK=fht32 only): single-precision FHT through nbl_create_fht32_wide, which takes check degrees up to
+	// NBL_FHT32_MAX_CHECK_DEGREE (off by default, NBL_FHT32_WIDE=0 names the default); the same two schedules
+	const char *fwenv = getenv("NBL_FHT32_WIDE");
+	const bool fwide = fwenv && std::string(fwenv) == "1";
+	if (fwenv && !fwide && std::string(fwenv) != "0") {
+		error = std::string("NBL_FHT32_WIDE=") + fwenv + ": unknown value (0, 1)";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	if (fwide && !fht32) {
+		error = "NBL_FHT32_WIDE=1: the wide single-precision FHT decoder goes with NBL_BP_CHECK=fht32 (log-QSPA, method 1, without OSD, under NBL_SCHEDULE=flooding or layered-bp)";
+		std::cerr << error << std::endl;
+		return false;
+	}
 	nbl_status st = bwide     ? nbl_create_bp_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_BP_WIDE_LAYERED : 0u, device, &dec)
+	                : fwide   ? nbl_create_fht32_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT32_WIDE_LAYERED : 0u, device, &dec)
 	                : twide   ? nbl_create_tems_wide(&code, mul.data(), inv.data(), &p, nullptr, damped ? NBL_TEMS_WIDE_LAYERED : 0u, device, &dec)
 	                : wide    ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)
 	                : fht32   ? nbl_create_fht32(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT32_LAYERED : 0u, device, &dec)
