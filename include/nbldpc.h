@@ -41,7 +41,8 @@ extern "C" {
 typedef enum nbl_status {
 	NBL_OK = 0,
 	NBL_ERR_ARG = -1,        /* bad argument / inconsistent graph (reference: undefined behaviour or exit(-1)) */
-	NBL_ERR_UNSUPPORTED = -2,/* method 3/5 (reference prints "not developed" and exits, NBLDPC.cpp:618-638), method 6 without
+	NBL_ERR_UNSUPPORTED = -2,/* method 3 outside nbl_create_minmax and method 5, which stays unbuilt (reference prints "not developed"
+	                            and exits, NBLDPC.cpp:618-638), method 6 without
 	                            nbl_create_osd's parameters, method 7 without nbl_create_ex's, a shape the kernels do not serve,
 	                            an OSD matrix that is too large or not of full row rank                                        */
 	NBL_ERR_NO_DEVICE = -3,  /* no HIP device: there is deliberately no CPU path                               */
@@ -448,6 +449,52 @@ nbl_status nbl_create_tems_wide(const nbl_code_desc *code, const uint16_t *gf_mu
 #define NBL_BP_WIDE_LAYERED 1u
 nbl_status nbl_create_bp_wide(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
                               const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
+
+/* ---- Min-Max decoding (method 3): flooding and layered, check degrees up to 32 -------------------------------------------------------
+ * The reference names the method (Simulation.h) and has no code for it; this is a decoder kind of this library, defined here operation
+ * by operation.  Conventions are the library's: a vector has q slots, slot 0 is 0; L[a] = ln P(a)/P(0), larger = more likely;
+ * DecideLLRVector is the decision rule everywhere.
+ *
+ * The Min-Max check-node update.  Inputs in_0 .. in_{dc-1} with edge coefficients h_d; all arithmetic is IEEE double; inputs are assumed
+ * finite.
+ *   1. Check domain: p_d[h_d a] = in_d[a], p_d[0] = 0.
+ *   2. Dissimilarities: m_d = max_y p_d[y], the slot 0 included, so m_d >= 0; u_d[y] = m_d - p_d[y]: one rounded subtraction, >= +0,
+ *      exactly +0 at the maximum.
+ *   3. Combination: w_d[y] = min over all (a_k), k != d, with XOR_k a_k = y, of max_{k != d} u_k[a_k].  This is a definition by SET:
+ *      evaluation order is immaterial, because min and max select and never round.  The forward / backward recursion with the elementary
+ *      step E(A,B)[c] = min_a max(A[a], B[a ^ c]) evaluates it exactly (max(min_i x_i, b) = min_i max(x_i, b)):
+ *        F_1 = u_0, F_{k+1} = E(F_k, u_k);   R_{dc-2} = u_{dc-1}, R_{k-1} = E(R_k, u_k);
+ *        w_0 = R_0, w_{dc-1} = F_{dc-1}, otherwise w_d = E(F_d, R_d);   for dc = 2: w_0 = u_1, w_1 = u_0.
+ *   4. Back to LLRs: c_d[y] = w_d[0] - w_d[y], one rounded subtraction, c_d[0] = 0.
+ *   5. Shaping and un-permuting: c2v_d[a] = shape(c_d[h_d a], ems_factor, ems_offset) for a != 0, where shape is what EMS applies to its
+ *      c2v values: the identity at factor 1 and offset 0, otherwise divide by the factor (when it is not 1), then the dead zone
+ *      (y < -offset: y + offset; y > offset: y - offset; else 0).  nbl_params keeps its layout: Min-Max reads ems_factor / ems_offset and
+ *      nothing else of the EMS fields.  ems_factor = 0 is NBL_ERR_ARG (the message names nbl_create_minmax and ems_factor).
+ * Every correct evaluation of this update gives the same bits, so parity with a restatement is equality, at every field and degree.
+ *
+ * Schedules.  Flooding: word for word the reference's EMS iteration (NBLDPC.cpp:805-918) with the update above in place of :859-917 --
+ * post in the variable's edge order, decision, syndrome, the freeze at the first zero syndrome, v2c = post - c2v, no damping.  Layered
+ * (NBL_MINMAX_LAYERED): word for word the schedule of nbl_create_layered with the same replacement -- the same layer rules,
+ * nbl_layer_greedy for layer_of == NULL, the same refusal texts for a bad assignment.
+ *
+ * nbl_create_minmax: params->method must be NBL_METHOD_MINMAX; any other method is NBL_ERR_UNSUPPORTED (the message names method 3).
+ *   flags 0 is flooding (a non-NULL layer_of is NBL_ERR_ARG); an unknown flag bit is NBL_ERR_ARG.  Check degrees 2 .. 32
+ *   (NBL_MINMAX_MAX_CHECK_DEGREE; a larger check is NBL_ERR_ARG, the message names this entry point, the degree found and 32); variable
+ *   degrees 1 .. 8, with nbl_create's text; q = 4 .. 256; every other refusal of nbl_create holds, with its status and text.  No OSD, no
+ *   extension parameters.  All of it before the device is touched.
+ *   One programme runs every degree and field under both schedules (nbl_debug_force_generic changes nothing): one check per workgroup of
+ *   max(1, q / 64) waves whose LDS holds the [maxdc][q] dissimilarities, two [q] operand blocks and two [q] output vectors:
+ *   (maxdc + 4) q 8 bytes, at most 73,728 at q = 256 and degree 32, so no shape is refused for its LDS.
+ *   nbl_read_state returns post (with nbl_set_record_state) and c2v; a non-NULL v2c is NBL_ERR_UNSUPPORTED.  nbl_get_layers works on the
+ *   layered kind and is NBL_ERR_ARG on the flooding kind.  Every decode entry point (host, device, bits, samples, prior, csi, idd,
+ *   resident, noise), soft output (plain and extrinsic), fixed_iters, poll_every and the active list, the transmitter, channel, fading and
+ *   error count work unchanged on such a decoder.
+ *   nbl_create, nbl_create_ex, nbl_create_osd and the nbl_create_layered* family keep refusing method 3 exactly as before. */
+#define NBL_METHOD_MINMAX 3
+#define NBL_MINMAX_LAYERED 1u
+#define NBL_MINMAX_MAX_CHECK_DEGREE 32
+nbl_status nbl_create_minmax(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                             const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out);
 
 /* L_ch: [B][N][q-1] doubles, L_ch[b][n][a-1] = ln P(x_n=a)/P(x_n=0)  (RX_LLR_SYM, Comm.cpp:340-407).
  * out_sym: [B][N] decided symbols (DecodeOutput).  converged: [B] 1 = zero syndrome reached (the

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NBL_HIP_LIB") or os.path.join(_HERE, "csrc", "libnbldpc_hip.so")  # NBL_HIP_LIB: A/B builds
 
 METHOD_BP, METHOD_EMS, METHOD_TEMS, METHOD_OSD, METHOD_BS_TEMS = 1, 2, 4, 6, 7
+METHOD_MINMAX = 3        # NBL_METHOD_MINMAX: through nbl_create_minmax alone (Decoder(..., minmax=True))
 DEMOD_LOGSUM, DEMOD_MAXLOG = 0, 1
 SOFT_LOGSUM, SOFT_MAXLOG = 0, 1
 SOFT_EXTRINSIC = 1
@@ -23,14 +24,16 @@ FHT32_WIDE_LAYERED = 1   # NBL_FHT32_WIDE_LAYERED
 EMS_WIDE_LAYERED = 1     # NBL_EMS_WIDE_LAYERED
 TEMS_WIDE_LAYERED = 1    # NBL_TEMS_WIDE_LAYERED
 BP_WIDE_LAYERED = 1      # NBL_BP_WIDE_LAYERED
+MINMAX_LAYERED = 1       # NBL_MINMAX_LAYERED
 # the entry points that name a decoder kind: the library's name of the kind -> (creation function, its layered flag)
 KIND_ENTRY = {"fht": ("nbl_create_fht", FHT_LAYERED), "fht32": ("nbl_create_fht32", FHT32_LAYERED), "fht32_wide": ("nbl_create_fht32_wide", FHT32_WIDE_LAYERED),
               "ems_wide": ("nbl_create_ems_wide", EMS_WIDE_LAYERED),
-              "tems_wide": ("nbl_create_tems_wide", TEMS_WIDE_LAYERED), "bp_wide": ("nbl_create_bp_wide", BP_WIDE_LAYERED)}
+              "tems_wide": ("nbl_create_tems_wide", TEMS_WIDE_LAYERED), "bp_wide": ("nbl_create_bp_wide", BP_WIDE_LAYERED),
+              "minmax": ("nbl_create_minmax", MINMAX_LAYERED)}
 FADING_NONE, FADING_RAYLEIGH = 0, 1
 
 # every symbol include/nbldpc.h declares
-EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_create_layered_bp", "nbl_create_fht", "nbl_create_ems_wide", "nbl_create_tems_wide", "nbl_create_bp_wide", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
+EXPORTS = ("nbl_abi_version", "nbl_create", "nbl_create_ex", "nbl_create_osd", "nbl_layer_greedy", "nbl_create_layered", "nbl_create_layered_ex", "nbl_create_layered_bp", "nbl_create_fht", "nbl_create_ems_wide", "nbl_create_tems_wide", "nbl_create_bp_wide", "nbl_create_minmax", "nbl_get_layers", "nbl_destroy", "nbl_decode_batch", "nbl_decode_batch_device",
            "nbl_set_demodulator", "nbl_set_demodulator_ex", "nbl_decode_batch_samples", "nbl_decode_batch_noise", "nbl_rand_advance", "nbl_channel_batch", "nbl_decode_batch_resident",
            "nbl_set_transmitter", "nbl_transmit_batch", "nbl_pn_advance", "nbl_count_errors", "nbl_encode_batch", "nbl_read_transmitted",
            "nbl_read_state", "nbl_set_record_state", "nbl_set_profiling", "nbl_last_timing", "nbl_last_error",
@@ -111,6 +114,8 @@ def load_library():
         L.nbl_create_layered_bp.restype = C.c_int
         L.nbl_create_layered_bp.argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         for fn, _ in KIND_ENTRY.values():   # one signature: (code, gf_mul, gf_inv, params, layer_of, flags, device, out)
+            if not hasattr(L, fn):          # (an NBL_HIP_LIB built from an older commit: the kind is an AttributeError where it is asked for)
+                continue
             getattr(L, fn).restype = C.c_int
             getattr(L, fn).argtypes = [C.POINTER(CodeDesc), C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.nbl_get_layers.restype = C.c_int
@@ -201,7 +206,7 @@ class PlanInfo(C.Structure):
 
 
 def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=None, bs_nc=2, layers=None, damped=None,
-               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False, fht32_wide=False):
+               force_generic=0, record_state=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False, fht32_wide=False, minmax=False):
     """The check-node kernel a decoder of this description would run (nbl_debug_plan; host arithmetic, no device, no decoder):
     (kernel name, fusable, fused, want_v2c).  The description is built the way Decoder builds it; layers / damped / fht as there
     (None = flooding), force_generic as nbl_debug_force_generic takes it (with fht, 3 names the wide programme, fht_wide /
@@ -210,10 +215,11 @@ def debug_plan(code, method, ems_nm=32, ems_nc=3, tems_nr=2, tems_nc=3, bs_nm=No
     degree where tems_nc <= 4; with bp_wide, the decoder nbl_create_bp_wide would make: 3 names bp_wide / bp_wide_layered at any check
     degree; with fht32, the decoder nbl_create_fht32 would make: fht32 / fht32_layered under every switch; with fht32_wide, the decoder
     nbl_create_fht32_wide would make: 3 names fht32_wide / fht32_wide_layered at any check degree), record_state as
-    nbl_set_record_state.  fht, wide, tems_wide, bp_wide, fht32 and fht32_wide exclude one another."""
-    kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32, fht32_wide=fht32_wide).items() if on]
+    nbl_set_record_state; with minmax (method 3), the decoder nbl_create_minmax would make: minmax / minmax_layered under every switch.
+    fht, wide, tems_wide, bp_wide, fht32, fht32_wide and minmax exclude one another."""
+    kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32, fht32_wide=fht32_wide, minmax=minmax).items() if on]
     if len(kinds) > 1:
-        raise ValueError("fht, wide, tems_wide, bp_wide, fht32 and fht32_wide name six different entry points: give one of them")
+        raise ValueError("fht, wide, tems_wide, bp_wide, fht32, fht32_wide and minmax name seven different entry points: give one of them")
     lib = load_library()
     params = Params(method, 0, ems_nm, ems_nc, 1.0, 0.0, tems_nr, tems_nc, 1.0, 0.0, 0, 0, 0)
     ext = ParamsExt(bs_nm, bs_nc, 1.0, 0.0) if bs_nm is not None else None
@@ -260,12 +266,15 @@ class Decoder:
     assignment; read_state and soft_output return doubles that are the exact widening of the float state.  fht32_wide=True (method 1
     only; without any of the other kind flags, bp, damped, OSD or extension parameters): nbl_create_fht32_wide, the same decoder with check
     degrees up to NBL_FHT32_MAX_CHECK_DEGREE = 32 (a code with a check above degree 8 runs the update with every transformed input scaled
-    by a power of two)."""
+    by a power of two).  minmax=True (method 3, METHOD_MINMAX, only; without any of the other kind flags, bp, damped, OSD or extension
+    parameters): nbl_create_minmax, Min-Max decoding with check degrees up to NBL_MINMAX_MAX_CHECK_DEGREE = 32 -- flooding without layers,
+    the layered schedule of nbl_create_layered with layers="greedy" or an assignment; ems_factor / ems_offset shape its c2v messages.
+    Without the flag method 3 goes to nbl_create, which refuses it."""
 
     def __init__(self, code, method, max_iter, ems_nm=32, ems_nc=3, ems_factor=1.0, ems_offset=0.0, tems_nr=2, tems_nc=3,
                  tems_factor=1.0, tems_offset=0.0, fixed_iters=0, poll_every=0, max_batch=0, device=0, gf=None,
                  bs_nm=None, bs_nc=2, bs_factor=1.0, bs_offset=0.0, osd_order=None, osd_flag=0, osd_factor=0.0, crc_len=8, crc_rows=0,
-                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False, fht32_wide=False):
+                 gf_mat=None, layers=None, damped=None, bp=False, fht=False, wide=False, tems_wide=False, bp_wide=False, fht32=False, fht32_wide=False, minmax=False):
         self.lib = load_library()
         self.code = code
         mul, inv = gf if gf is not None else datafiles.gf_tables(code.q)
@@ -299,6 +308,9 @@ class Decoder:
         if fht32_wide and (fht32 or fht or bp or damped is not None or wide or tems_wide or bp_wide or osd_order is not None or bs_nm is not None):
             raise ValueError("fht32_wide: nbl_create_fht32_wide takes no fht32 / fht / bp / damped / wide / tems_wide / bp_wide flag and neither OSD nor extension "
                              "parameters (layers alone picks its schedule)")
+        if minmax and (fht32_wide or fht32 or fht or bp or damped is not None or wide or tems_wide or bp_wide or osd_order is not None or bs_nm is not None):
+            raise ValueError("minmax: nbl_create_minmax takes no fht32_wide / fht32 / fht / bp / damped / wide / tems_wide / bp_wide flag and neither OSD nor "
+                             "extension parameters (layers alone picks its schedule)")
         lay = None
         if layers is not None:
             if osd_order is not None or bs_nm is not None:
@@ -308,7 +320,7 @@ class Decoder:
                 raise ValueError(f"layers must be 'greedy' or one layer per check ({code.M}), got shape {self._layer_of.shape}")
             lay = None if self._layer_of is None else self._layer_of.ctypes.data
         # (at most one of the kinds: every pair is refused above)
-        kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32, fht32_wide=fht32_wide).items() if on]
+        kinds = [k for k, on in dict(fht=fht, ems_wide=wide, tems_wide=tems_wide, bp_wide=bp_wide, fht32=fht32, fht32_wide=fht32_wide, minmax=minmax).items() if on]
         if kinds:
             fn, layered_flag = KIND_ENTRY[kinds[0]]
             rc = getattr(self.lib, fn)(C.byref(desc), self._mul.ctypes.data, self._inv.ctypes.data, C.byref(self.params), lay,

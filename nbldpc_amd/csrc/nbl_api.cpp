@@ -120,7 +120,7 @@ nbl_status ensure_workspace(nbl_decoder *d, int B)
 	make(b.post, want_post, (size_t)cap * N * q * 8);
 	make(b.osd_S, d->osd_acc, (size_t)cap * N * d->g.p * 8);
 	make(b.dec, true, (size_t)cap * N * 4);
-	make(b.edge_dec, d->prm.method != NBL_METHOD_EMS, (size_t)cap * E * 4);
+	make(b.edge_dec, d->prm.method != NBL_METHOD_EMS && d->kind != NBL_KIND_MINMAX, (size_t)cap * E * 4); // (the damped methods' state)
 	make(b.out, true, (size_t)cap * N * 4);
 	make(b.iters, true, (size_t)cap * 4);
 	make(b.done, true, (size_t)cap);
@@ -181,7 +181,7 @@ extern "C" nbl_status nbl_set_profiling(nbl_decoder *d, int32_t on)
 // fused iteration (2); on an nbl_create_fht decoder 3 selects the wide programme (nbl_cn_fht_wide.hip) at any check degree, on an
 // nbl_create_ems_wide decoder the workgroup-per-check programme (nbl_cn_ems_wide.hip), on an nbl_create_tems_wide decoder with
 // tems_nc <= NBL_TEMS_WIDE_MAX_NC that of nbl_cn_tems_wide.hip, on an nbl_create_bp_wide decoder that of nbl_cn_bp_wide.hip, on an
-// nbl_create_fht32_wide decoder that of nbl_cn_fht32_wide.hip.
+// nbl_create_fht32_wide decoder that of nbl_cn_fht32_wide.hip.  An nbl_create_minmax decoder has one programme: no value moves it.
 extern "C" nbl_status nbl_debug_force_generic(nbl_decoder *d, int32_t on)
 {
 	if (!d) return NBL_ERR_ARG;
@@ -268,7 +268,7 @@ extern "C" nbl_status nbl_debug_plan(const nbl_code_desc *code, const nbl_params
 	return plan_info(code, params, NBL_KIND_BASE, layered_flags >= 0, force_generic, record_state, out);
 }
 
-// The decoder the entry point of a kind would make.  kind_name: "fht", "fht32", "fht32_wide", "ems_wide", "tems_wide" or "bp_wide" (NblEntry::name);
+// The decoder the entry point of a kind would make.  kind_name: "fht", "fht32", "fht32_wide", "ems_wide", "tems_wide", "bp_wide" or "minmax" (NblEntry::name);
 // layered: nonzero = with the kind's NBL_*_LAYERED flag
 extern "C" nbl_status nbl_debug_plan_kind(const nbl_code_desc *code, const nbl_params *params, const char *kind_name, int32_t layered,
                                           int32_t force_generic, int32_t record_state, nbl_plan_info *out)
@@ -288,6 +288,10 @@ extern "C" uint64_t nbl_debug_tems_wide_lds_bytes(int32_t q, int32_t maxdc, int3
 // Diagnostic only (not part of include/nbldpc.h): the bytes of LDS one check of the wide log-QSPA programme takes -- the one function both
 // launchers size by (below 160 KB for every shape the ABI accepts: creation has nothing to refuse)
 extern "C" uint64_t nbl_debug_bp_wide_lds_bytes(int32_t q, int32_t maxdc) { return nbl_bp_wide_lds_bytes(q, maxdc); }
+
+// Diagnostic only (not part of include/nbldpc.h): the bytes of LDS one check of an nbl_create_minmax decoder takes -- the one function both
+// launchers size by, and the figure include/nbldpc.h quotes
+extern "C" uint64_t nbl_debug_minmax_lds_bytes(int32_t q, int32_t maxdc) { return nbl_minmax_lds_bytes(q, maxdc); }
 
 // Diagnostic only (not part of include/nbldpc.h): the path code (nbl_tems_path.h) of the path that deviates to syms[i] in column cols[i],
 // i < n <= NBL_TEMS_WIDE_MAX_NC, columns ascending -- built by the kernels' own append, one deviation after the other; 0 for arguments
@@ -323,6 +327,7 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 {
 	const NblGraphDev &g = d->g;
 	const bool f32 = nbl_kind_f32(d->kind); // (NblPlan::f32: the FHT kinds run by their binary32 instances on the float state)
+	const bool mm = d->kind == NBL_KIND_MINMAX; // (NblPlan::minmax: the launch shape of the wide EMS kinds, run by the Min-Max programme)
 	if (cn_is_layered(cn) != (lr != nullptr)) { d->err = "layered schedule: no layered check-node kernel for this method"; return NBL_ERR_UNSUPPORTED; }
 	const int off = lr ? lr->off : 0, cnt = lr ? lr->cnt : 0;
 	switch (cn) {
@@ -340,7 +345,7 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_BP: HIP_TRY(d, nbl_launch_cn_bp(g, w, r, st)); break;
 	case NBL_CN_FHT: HIP_TRY(d, f32 ? nbl_launch_cn_fht32(g, w, d->w32, r, st) : nbl_launch_cn_fht(g, w, r, st)); break;
 	case NBL_CN_FHT_WIDE: HIP_TRY(d, f32 ? nbl_launch_cn_fht32_wide(g, w, d->w32, r, st) : nbl_launch_cn_fht_wide(g, w, r, st)); break;
-	case NBL_CN_EMS_WIDE: HIP_TRY(d, nbl_launch_cn_ems_wide(g, w, r, st)); break;
+	case NBL_CN_EMS_WIDE: HIP_TRY(d, mm ? nbl_launch_cn_minmax(g, w, r, st) : nbl_launch_cn_ems_wide(g, w, r, st)); break;
 	case NBL_CN_TEMS_WIDE: HIP_TRY(d, nbl_launch_cn_tems_wide(g, w, r, st)); break;
 	case NBL_CN_BP_WIDE: HIP_TRY(d, nbl_launch_cn_bp_wide(g, w, r, st)); break;
 	case NBL_CN_BSTEMS: HIP_TRY(d, nbl_launch_cn_bstems(g, w, r, st)); break;
@@ -350,7 +355,9 @@ static nbl_status launch_cn(nbl_decoder *d, NblCn cn, const NblWork &w, const Nb
 	case NBL_CN_FHT_LAYERED:
 		HIP_TRY(d, f32 ? nbl_launch_cn_fht32_layered(g, w, d->w32, r, d->ly, off, cnt, st) : nbl_launch_cn_fht_layered(g, w, r, d->ly, off, cnt, st));
 		break;
-	case NBL_CN_EMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_ems_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
+	case NBL_CN_EMS_WIDE_LAYERED:
+		HIP_TRY(d, mm ? nbl_launch_cn_minmax_layered(g, w, r, d->ly, off, cnt, st) : nbl_launch_cn_ems_wide_layered(g, w, r, d->ly, off, cnt, st));
+		break;
 	case NBL_CN_TEMS_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_tems_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
 	case NBL_CN_BP_WIDE_LAYERED: HIP_TRY(d, nbl_launch_cn_bp_wide_layered(g, w, r, d->ly, off, cnt, st)); break;
 	case NBL_CN_FHT_WIDE_LAYERED:
@@ -526,12 +533,13 @@ nbl_status run_iterations(nbl_decoder *d, const double *d_Lin, int B, hipStream_
 	c.d = d;
 	d->pending.on = false; // (a pass the last decode left pending is dropped: nobody read that state)
 	d->idd_sub = false; // (the loop sets it again after its last pass)
-	c.damp = p.method != NBL_METHOD_EMS;
+	const bool as_ems = p.method == NBL_METHOD_EMS || d->kind == NBL_KIND_MINMAX; // (Min-Max: the EMS iteration around its own check node)
+	c.damp = !as_ems;
 	NblRun &r = c.r;
 	r = NblRun{};
 	r.B = B;
 	r.fixed_iters = p.fixed_iters;
-	if (p.method == NBL_METHOD_EMS) { r.nm = p.ems_nm; r.nc = p.ems_nc; r.factor = p.ems_factor; r.offset = p.ems_offset; }
+	if (as_ems) { r.nm = p.ems_nm; r.nc = p.ems_nc; r.factor = p.ems_factor; r.offset = p.ems_offset; }
 	else if (p.method == NBL_METHOD_BS_TEMS) { r.nm = d->ext.bs_nm; r.nc = d->ext.bs_nc; r.factor = d->ext.bs_factor; r.offset = d->ext.bs_offset; }
 	else { r.nr = p.tems_nr; r.nc = p.tems_nc; r.factor = p.tems_factor; r.offset = p.tems_offset; }
 	r.damp_old = (p.method == NBL_METHOD_BP) ? 0.5 : 0.25;  // NBLDPC.cpp:739 / :1046 / :1262
@@ -745,7 +753,8 @@ extern "C" nbl_status nbl_read_state(nbl_decoder *d, int32_t b, double *post, do
 		else rc = grab(d->w.post + (size_t)b * N * q, nullptr, N, post);
 	}
 	if (!rc && v2c) {
-		if (d->layered && d->prm.method == NBL_METHOD_EMS) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
+		if (d->kind == NBL_KIND_MINMAX) { d->err = "a Min-Max decoder returns no v2c (as the EMS decoders: post and c2v are its state)"; rc = NBL_ERR_UNSUPPORTED; }
+		else if (d->layered && d->prm.method == NBL_METHOD_EMS) { d->err = "the layered schedule never materialises v2c (a check forms its inputs from L_ch and c2v)"; rc = NBL_ERR_UNSUPPORTED; }
 		else if (!d->w.v2c) { d->err = "v2c is not kept in HBM on the fused path unless state recording is on (nbl_set_record_state)"; rc = NBL_ERR_ARG; }
 		else rc = grab(d->w.v2c + (size_t)b * E * q, nullptr, E, v2c);
 	}

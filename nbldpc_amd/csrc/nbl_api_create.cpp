@@ -310,6 +310,12 @@ static const NblEntry nbl_entries[] = {
 	{NBL_KIND_BP_WIDE, "bp_wide", "nbl_create_bp_wide", NBL_BP_WIDE_LAYERED, "NBL_BP_WIDE_LAYERED", NBL_METHOD_BP,
 	 " runs exact log-QSPA (method 1) only: the other methods keep their entry points (EMS above check degree 8: nbl_create_ems_wide, T-EMS: nbl_create_tems_wide)",
 	 NBL_BP_MAX_CHECK_DEGREE, "", 0, true},
+	// Min-Max, the same shape of programme; (maxdc + 4) q 8 bytes of LDS, at most 73,728 B -- nothing to refuse for LDS.  Layered:
+	// nbl_create_layered
+	{NBL_KIND_MINMAX, "minmax", "nbl_create_minmax", NBL_MINMAX_LAYERED, "NBL_MINMAX_LAYERED", NBL_METHOD_MINMAX,
+	 " runs Min-Max (method 3) only: the other methods keep their entry points (EMS: nbl_create / nbl_create_ems_wide, T-EMS: nbl_create_tems_wide, log-QSPA: "
+	 "nbl_create_bp_wide / nbl_create_fht)",
+	 NBL_MINMAX_MAX_CHECK_DEGREE, "", 0, false},
 };
 
 const NblEntry *nbl_entry(NblKind kind)
@@ -378,6 +384,12 @@ extern "C" nbl_status nbl_create_bp_wide(const nbl_code_desc *code, const uint16
 	return create_kind(NBL_KIND_BP_WIDE, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
 }
 
+extern "C" nbl_status nbl_create_minmax(const nbl_code_desc *code, const uint16_t *gf_mul, const uint16_t *gf_inv, const nbl_params *params,
+                                        const int32_t *layer_of, uint32_t flags, int device, nbl_decoder **out)
+{
+	return create_kind(NBL_KIND_MINMAX, code, gf_mul, gf_inv, params, layer_of, flags, device, out);
+}
+
 extern "C" nbl_status nbl_get_layers(const nbl_decoder *d, int32_t *layer_of, int32_t *n_layers)
 {
 	if (!d || !d->layered) return NBL_ERR_ARG;
@@ -391,6 +403,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 {
 	const NblEntry *const en = nbl_entry(kind); // NULL: nbl_create* / nbl_create_layered*
 	const bool ems_wide = kind == NBL_KIND_EMS_WIDE, tems_wide = kind == NBL_KIND_TEMS_WIDE;
+	const bool minmax = kind == NBL_KIND_MINMAX; // (method 3 has passed the entry's own method check below: its schedule is that of EMS)
 	if (!out) return NBL_ERR_ARG;
 	*out = nullptr;
 	if (!code || !gf_mul || !gf_inv || !params) return fail_create(nullptr, NBL_ERR_ARG, "null argument");
@@ -410,10 +423,11 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (lay && !lay->bp && (lay->flags & NBL_LAYERED_DAMPED) && params->method != NBL_METHOD_EMS && params->method != NBL_METHOD_TEMS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the damped layered schedule (NBL_LAYERED_DAMPED) is defined for T-EMS (method 4), and for EMS (method 2), which "
 		                                                 "has no damping, as the plain layered schedule: log-QSPA (method 1) and BS-TEMS (method 7) stay flooding-only");
-	if (lay && !lay->bp && params->method != NBL_METHOD_EMS && !((lay->flags & NBL_LAYERED_DAMPED) && params->method == NBL_METHOD_TEMS))
+	if (lay && !lay->bp && !minmax && params->method != NBL_METHOD_EMS && !((lay->flags & NBL_LAYERED_DAMPED) && params->method == NBL_METHOD_TEMS))
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "the layered schedule is defined for EMS (method 2) only: the other methods damp against the previous iteration's "
 		                                                 "decision in their variable-node pass and stay flooding-only");
-	switch (params->method) {
+	// (method 3 through nbl_create_minmax alone: every other entry point takes the default's refusal, as before)
+	switch (minmax ? NBL_METHOD_EMS : params->method) {
 	case NBL_METHOD_EMS: case NBL_METHOD_BP: case NBL_METHOD_TEMS: break;
 	case NBL_METHOD_BS_TEMS:
 		if (!ext) return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "BS-TEMS (method 7): its parameters (bs_nm, bs_nc, bs_factor, bs_offset) go through nbl_create_ex");
@@ -468,6 +482,8 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		if (params->ems_nm > q) return fail_create(nullptr, NBL_ERR_ARG, "EMS configuration error! EMS_Nm is too large!");
 		if (params->ems_nm < 1 || params->ems_nc < 0) return fail_create(nullptr, NBL_ERR_ARG, "ems_nm < 1 or ems_nc < 0");
 	}
+	// (Min-Max reads its shaping from the EMS fields; nm and nc are not read)
+	if (minmax && !(params->ems_factor != 0.0)) return fail_create(nullptr, NBL_ERR_ARG, "nbl_create_minmax: ems_factor must be non-zero (c2v values are divided by it)");
 	if (params->method == NBL_METHOD_TEMS && (params->tems_nr < 1 || params->tems_nc < 0))
 		return fail_create(nullptr, NBL_ERR_ARG, "tems_nr < 1 or tems_nc < 0");
 	if (params->method == NBL_METHOD_BS_TEMS) {

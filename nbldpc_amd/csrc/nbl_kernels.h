@@ -89,6 +89,16 @@ size_t nbl_bp_wide_lds_bytes(int q, int maxdc);
 hipError_t nbl_launch_cn_bp_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_bp_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
+// Min-Max check node (method 3; nbl_create_minmax; nbl_cn_minmax.hip): the programme of nbl_cn_minmax_core.h, one check per workgroup of
+// max(1, q / 64) waves, check degrees up to NBL_MINMAX_MAX_CHECK_DEGREE, flooding (inputs: w.v2c) and the checks of one layer (inputs:
+// L_ch and the in-place c2v).  LDS of one workgroup: (maxdc + 4) q 8 bytes, at most 73,728 B (q = 256, degree 32) -- below
+// NBL_MINMAX_MAX_LDS for every shape the ABI accepts, so nbl_create_minmax refuses no shape for LDS; both launchers size by the one
+// function and check the bound all the same
+#define NBL_MINMAX_MAX_LDS (160 * 1024)
+size_t nbl_minmax_lds_bytes(int q, int maxdc);
+hipError_t nbl_launch_cn_minmax(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
+hipError_t nbl_launch_cn_minmax_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
+
 // specialised EMS check node (nbl_cn_ems256.hip)
 size_t nbl_ems256_lds_bytes(int nm);
 hipError_t nbl_launch_cn_ems256(const NblGraphDev &g, const NblWork &w, const NblRun &r, bool fused, hipStream_t st);

@@ -39,6 +39,7 @@ static const char *const cn_names[NBL_CN_COUNT] = {
 const char *nbl_cn_name(NblCn cn) { return cn_names[cn]; }
 const char *nbl_plan_name(const NblPlan &plan)
 {
+	if (plan.minmax) return plan.cn == NBL_CN_EMS_WIDE_LAYERED ? "minmax_layered" : "minmax";
 	if (!plan.f32) return cn_names[plan.cn];
 	switch (plan.cn) {
 	case NBL_CN_FHT_LAYERED: return "fht32_layered";
@@ -61,8 +62,15 @@ NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const NblPlanReq &rq)
 {
 	const bool layered = rq.layered, record_state = rq.record_state, small_on = rq.small_on;
 	const int force_generic = rq.force_generic;
-	NblPlan pl{NBL_CN_NONE, false, false, true, false};
+	NblPlan pl{NBL_CN_NONE, false, false, true, false, false};
 	switch (rq.kind) {
+	case NBL_KIND_MINMAX:
+		// one programme for every degree and field, in the launch shape of the wide EMS kinds: never fused, no debug switch moves it.
+		// Flooding reads the v2c of the variable-node pass; layered forms its inputs from L_ch and c2v
+		pl.cn = layered ? NBL_CN_EMS_WIDE_LAYERED : NBL_CN_EMS_WIDE;
+		pl.minmax = true;
+		pl.want_v2c = !layered;
+		return pl;
 	case NBL_KIND_FHT32_WIDE:
 		// the scaled programme in the degree-independent layout: a code with a larger check than the register programme holds, or
 		// switch 3 at any degree; never fused; both schedules read the float v2c.  Any other request: the plan of NBL_KIND_FHT32

@@ -25,6 +25,9 @@ struct NblPlan {
 	bool want_v2c; // v2c exists in HBM: something reads it (the unfused path, the damped methods, state read-back)
 	bool f32;      // nbl_create_fht32 / nbl_create_fht32_wide: cn (fht, fht_layered, fht_wide or fht_wide_layered) is run by its binary32
 	               // instance on the float message state; named fht32 / fht32_layered / fht32_wide / fht32_wide_layered
+	bool minmax;   // nbl_create_minmax: cn (ems_wide or ems_wide_layered: the launch shape, the input formers and the buffers are those) is run
+	               // by the Min-Max programme (nbl_cn_minmax.hip); named minmax / minmax_layered.  A flag beside cn, as f32 is: NblCn lists
+	               // the kernels tests/test_idd_kinds.py wants a loop cell for, and Min-Max pins its loop in tests/test_gpu_minmax.py
 };
 
 // Which entry point made the decoder.  The kinds exclude one another; each non-base kind runs one method (nbl_entries, nbl_decoder.h):
@@ -48,7 +51,9 @@ struct NblPlan {
 //   FHT32_WIDE nbl_create_fht32_wide (method 1): a code with a check above degree NBL_MAXDC runs fht_wide / fht_wide_layered in binary32
 //              (NblPlan::f32; named fht32_wide / fht32_wide_layered) under every switch; any other code gets the plan of
 //              nbl_create_fht32, except that force_generic 3 selects the wide programme
-enum NblKind { NBL_KIND_BASE, NBL_KIND_FHT, NBL_KIND_FHT32, NBL_KIND_EMS_WIDE, NBL_KIND_TEMS_WIDE, NBL_KIND_BP_WIDE, NBL_KIND_FHT32_WIDE };
+//   MINMAX     nbl_create_minmax (method 3): minmax / minmax_layered (NblPlan::minmax), one programme for every check degree and field;
+//              never fused; flooding keeps v2c, layered has none; no debug switch moves it
+enum NblKind { NBL_KIND_BASE, NBL_KIND_FHT, NBL_KIND_FHT32, NBL_KIND_EMS_WIDE, NBL_KIND_TEMS_WIDE, NBL_KIND_BP_WIDE, NBL_KIND_FHT32_WIDE, NBL_KIND_MINMAX };
 // the kinds whose iterations run on the float message state (NblWork32): the float workspace, widen_state, the binary32 launchers
 inline bool nbl_kind_f32(NblKind kind) { return kind == NBL_KIND_FHT32 || kind == NBL_KIND_FHT32_WIDE; }
 
@@ -65,7 +70,7 @@ NblPlan nbl_plan(const NblShape &s, const nbl_params &prm, const NblPlanReq &rq)
 // the codes only the wide T-EMS programme runs (creation refuses tems_nc > NBL_TEMS_WIDE_MAX_NC there)
 inline bool nbl_tems_needs_wide(const NblShape &s) { return s.maxdc > NBL_MAXDC || s.p * s.maxdc > 32; }
 const char *nbl_cn_name(NblCn cn);
-const char *nbl_plan_name(const NblPlan &plan); // nbl_cn_name(plan.cn), or fht32[_wide][_layered] for a binary32 plan
+const char *nbl_plan_name(const NblPlan &plan); // nbl_cn_name(plan.cn), or fht32[_wide][_layered] for a binary32 plan, minmax[_layered] for a Min-Max plan
 
 // What each specialised kernel can run, beside the kernel (its LDS arithmetic lives there); nbl_plan is the only caller.
 // method: NBL_METHOD_* of include/nbldpc.h.  Unfused: any variable degrees.  Fused: NblShape::has_c_nbr for the small-field and the

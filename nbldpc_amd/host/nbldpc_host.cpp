@@ -92,6 +92,12 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 	// the q-1 entries of ./SRC/Mat.Repr.GF.<q>.txt (GF.cpp:115-152), so alpha^(q-2)'s matrix stays zero.  (The reference's order-3
 	// loop also prints "mm" for every frame, OSD.h:166; that debug print is not reproduced.)
 	const bool osd = sim.decodeMethod == OSD_DECODE || sim.OSD_order >= 0;
+	const bool minmax = sim.decodeMethod == MinMax_DECODE; // (through nbl_create_minmax, below)
+	if (minmax && osd) {
+		error = "DecodeMethod = 3: Min-Max decoding (nbl_create_minmax) has no OSD stage: set OSD_order below 0";
+		std::cerr << error << std::endl;
+		return false;
+	}
 	std::vector<uint8_t> gf_mat;
 	if (osd && !LoadMatRepr(gf_mat)) return false;
 	nbl_osd_params op = {sim.OSD_order, sim.OSD_flag, sim.OSD_factor, sim.crcLen, sim.crc_correctLen, gf_mat.data()};
@@ -193,7 +199,15 @@ bool CNBLDPC::Initial(CSimulation &sim, int device, int fixed_iters)
 		std::cerr << error << std::endl;
 		return false;
 	}
-	nbl_status st = bwide     ? nbl_create_bp_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_BP_WIDE_LAYERED : 0u, device, &dec)
+	// DecodeMethod = 3: Min-Max through nbl_create_minmax, shaping from the profile's EMS factor / offset, under NBL_SCHEDULE=flooding (or
+	// unset) and layered.  No switch: nothing else can be meant by method 3.  No OSD, and none of the switches of the other kinds
+	if (minmax && (damped || lay_bp || fht || fht32 || wide || twide || bwide || fwide)) {
+		error = "DecodeMethod = 3: the Min-Max decoder is defined for Min-Max (method 3) without OSD only, under NBL_SCHEDULE=flooding or layered";
+		std::cerr << error << std::endl;
+		return false;
+	}
+	nbl_status st = minmax    ? nbl_create_minmax(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_MINMAX_LAYERED : 0u, device, &dec)
+	                : bwide   ? nbl_create_bp_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_BP_WIDE_LAYERED : 0u, device, &dec)
 	                : fwide   ? nbl_create_fht32_wide(&code, mul.data(), inv.data(), &p, nullptr, lay_bp ? NBL_FHT32_WIDE_LAYERED : 0u, device, &dec)
 	                : twide   ? nbl_create_tems_wide(&code, mul.data(), inv.data(), &p, nullptr, damped ? NBL_TEMS_WIDE_LAYERED : 0u, device, &dec)
 	                : wide    ? nbl_create_ems_wide(&code, mul.data(), inv.data(), &p, nullptr, layered ? NBL_EMS_WIDE_LAYERED : 0u, device, &dec)

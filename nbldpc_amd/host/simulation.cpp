@@ -105,6 +105,7 @@ int CSimulation::Show(int mode)
 		else if (decodeMethod == BS_TEMS_DECODE)
 			cout << "Algorithm: BS_TEMS_DECODE\tBS_TEMS_Nm: " << bs_tems_nm << "\tBS_TEMS_Nc: " << bs_tems_nc << "\tFactor: " << bs_tems_factor
 			     << "\tOffset: " << bs_tems_offset << endl;
+		else if (decodeMethod == MinMax_DECODE) cout << "Algorithm: Min-Max\tFactor: " << ems_factor << "\tOffset: " << ems_offset << endl;
 		else if (decodeMethod == OSD_DECODE) cout << "Algorithm: " << "OSD" << endl;
 		else cout << "Algorithm: method " << decodeMethod << " (not available on this decode path)" << endl;
 		cout << "Modulation: " << nQAM << "-QAM" << "\tConf: " << ConstellationFileName << endl;
