@@ -544,9 +544,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 	if (params->method == NBL_METHOD_TEMS && !tems_wide && p * maxdc > 32)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: log2(q) * (largest check degree) must not exceed 32 (the trellis path code is one 32-bit word)");
 	// (a wide decoder with maxdc <= NBL_MAXDC may run either programme: both bounds hold, the general kernel's first, with nbl_create's text)
-	if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024)
+	if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > NBL_MAX_LDS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
-	if (ems_wide && nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > NBL_EMS_WIDE_MAX_LDS)
+	if (ems_wide && nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > NBL_MAX_LDS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_ems_wide: this (q, check degree, nm, nc) needs " +
 		                                                 std::to_string(nbl_ems_wide_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc)) +
 		                                                 " bytes of LDS per check, more than the 160 KB (163840 bytes) one workgroup can have");
@@ -554,7 +554,7 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide: tems_nc = " + std::to_string(params->tems_nc) + " above " + std::to_string(NBL_TEMS_WIDE_MAX_NC) +
 		                                                 " (NBL_TEMS_WIDE_MAX_NC: the deviations one 64-bit path code holds) on a code whose checks need the wide programme");
 	// (inside nbl_create's envelope the bound holds wherever switch 3 may select the wide programme; it is far from it there)
-	if (tems_wide && params->tems_nc <= NBL_TEMS_WIDE_MAX_NC && nbl_tems_wide_lds_bytes(q, maxdc, params->tems_nr, params->tems_nc) > NBL_TEMS_WIDE_MAX_LDS)
+	if (tems_wide && params->tems_nc <= NBL_TEMS_WIDE_MAX_NC && nbl_tems_wide_lds_bytes(q, maxdc, params->tems_nr, params->tems_nc) > NBL_MAX_LDS)
 		return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "nbl_create_tems_wide: this (q, check degree, nr, nc) needs " +
 		                                                 std::to_string(nbl_tems_wide_lds_bytes(q, maxdc, params->tems_nr, params->tems_nc)) +
 		                                                 " bytes of LDS per check, more than the 160 KB (163840 bytes) one workgroup can have");
@@ -570,9 +570,9 @@ static nbl_status create_impl(const nbl_code_desc *code, const uint16_t *gf_mul,
 		// 65,536 B at q = 256 and degree 32, what a launch gets without opting in -- nothing to refuse either; in single precision
 		// maxdc q 4 bytes, half of that)
 		if (params->method == NBL_METHOD_TEMS) {
-			if (!tems_needs_wide && nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > 160 * 1024)
+			if (!tems_needs_wide && nbl_tems_layered_lds_bytes(q, maxdc, params->tems_nc) > NBL_MAX_LDS)
 				return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "T-EMS: this (q, check degree, nc) needs more than the 160 KB of LDS one wave can have");
-		} else if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > 160 * 1024) {
+		} else if (params->method == NBL_METHOD_EMS && !(ems_wide && maxdc > NBL_MAXDC) && nbl_ems_lds_bytes(q, maxdc, params->ems_nm, params->ems_nc) > NBL_MAX_LDS) {
 			return fail_create(nullptr, NBL_ERR_UNSUPPORTED, "EMS: this (q, check degree, nm, nc) needs more than the 160 KB of LDS one wave can have");
 		}
 		layer_of.assign(M, 0);

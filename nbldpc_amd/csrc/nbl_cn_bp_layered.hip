@@ -15,50 +15,27 @@
 //   * an edge belongs to one check, so its v2c vector is read and written by that check's wave alone;
 //   * the launches of one stream order the layers.
 #include <hip/hip_runtime.h>
-#include "nbl_device.h"
-#include "nbl_kernels.h"
+#include "nbl_cn_shell.h"
 #include "nbl_cn_bp_core.h"
 #include "nbl_cn_bp_inputs.h"
 
-// the checks of one layer: one wave per (codeword, check); grid = count * (codeword slots)
+// the checks of one layer: one wave per (codeword, check)
 template <int Q>
 __global__ __launch_bounds__(64) void cn_bp_layered_kernel(NblGraphDev g, NblWork w, NblRun r, NblLayerDev ly, int offset, int count)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	const int lane = lane_id();
-	const int b = nbl_codeword(w, r, blockIdx.x / count), m = ly.chk[offset + blockIdx.x % count];
+	const int b = nbl_layer_codeword(w, r, count);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
-	const double *L = w.Lch + (size_t)b * g.N * Q;
-	double *Cb = w.c2v + (size_t)b * g.E * Q;
-	double *Vb = w.v2c + (size_t)b * g.E * Q;
-	// (the input former of the damped layered schedule: nbl_cn_bp_inputs.h, shared with nbl_cn_fht_layered.hip)
-	const BpLayeredInput<Q> input = {L, Cb, Vb, ly.nbr, g.c_epos, c0, lane, r.damp_old, r.damp_new};
-	bp_check_node<Q>(g, smem, c0, dc, Cb + (size_t)c0 * Q, input);
+	const NblCheck k = nbl_layer_check(g, ly, offset, count, b);
+	double *Cb = w.c2v + (size_t)k.b * g.E * Q;
+	const BpLayeredInput<Q> input = {w.Lch + (size_t)k.b * g.N * Q, Cb, w.v2c + (size_t)k.b * g.E * Q, ly.nbr, g.c_epos, k.c0, lane_id(), r.damp_old, r.damp_new};
+	bp_check_node<Q>(g, smem, k.c0, k.dc, Cb + (size_t)k.c0 * Q, input);
 }
-
-#define NBL_LAYERED_Q(q, ...)                                   \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
 
 hipError_t nbl_launch_cn_bp_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st)
 {
 	// (3 maxdc + 5) q 8 bytes: 59,392 B at q = 256 and degree 8, the largest the ABI accepts -- below the 64 KB a kernel has unasked
 	const size_t lds = nbl_bp_lds_bytes(g.q, g.maxdc);
-	const long long blocks = (long long)r.B * count;
-	if (count < 1 || offset < 0 || offset + count > g.M || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-	if (lds > 64 * 1024) return hipErrorInvalidValue;
-	if (!w.v2c) return hipErrorInvalidValue;
-	dim3 grid((unsigned)blocks), block(64);
-	NBL_LAYERED_Q(g.q, { cn_bp_layered_kernel<QQ><<<grid, block, lds, st>>>(g, w, r, ly, offset, count); })
-	return hipGetLastError();
+	if (!nbl_layer_range_ok(g, offset, count) || lds > NBL_LDS_OPT_IN || !w.v2c) return hipErrorInvalidValue;
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_bp_layered_kernel<QQ>, (long long)r.B * count, 64, lds, st, g, w, r, ly, offset, count))
 }

@@ -21,8 +21,7 @@
 // The reference keeps the configuration cost as a running sum (+= on the way in, -= on the way out); its residue is not
 // reproduced, and exact ties in LLV are ordered by symbol.
 #include <hip/hip_runtime.h>
-#include "nbl_device.h"
-#include "nbl_kernels.h"
+#include "nbl_cn_shell.h"
 
 #define NBL_BS_MAXNM 16
 
@@ -33,10 +32,10 @@ __global__ __launch_bounds__(64) void cn_bstems_kernel(NblGraphDev g, NblWork w,
 	constexpr int P = Fld<Q>::P;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	const int lane = lane_id();
-	const int b = nbl_codeword(w, r, blockIdx.x / g.M), m = blockIdx.x % g.M;
+	const int b = nbl_flooding_codeword(g, w, r);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
+	const NblCheck k = nbl_flooding_check(g, b);
+	const int c0 = k.c0, dc = k.dc;
 	const int nm = r.nm, nc = r.nc, mdc = g.maxdc;
 
 	double *dU = (double *)smem;                   // [mdc][Q]
@@ -268,23 +267,11 @@ size_t nbl_bstems_lds_bytes(const NblGraphDev &g)
 bool nbl_bstems_applicable(const NblGraphDev &g, int nm, int nc)
 {
 	return nm >= 1 && nm <= NBL_BS_MAXNM && nm < g.q && nc >= 0 && g.maxdc <= 8 && g.q >= 4 && g.q <= 256 &&
-	       nbl_bstems_lds_bytes(g) <= 64 * 1024;
+	       nbl_bstems_lds_bytes(g) <= NBL_LDS_OPT_IN;
 }
 
 hipError_t nbl_launch_cn_bstems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st)
 {
 	if (!nbl_bstems_applicable(g, r.nm, r.nc)) return hipErrorInvalidValue;
-	const size_t lds = nbl_bstems_lds_bytes(g);
-	dim3 grid((unsigned)((long long)r.B * g.M)), block(64);
-	switch (g.q) {
-	case 4: cn_bstems_kernel<4><<<grid, block, lds, st>>>(g, w, r); break;
-	case 8: cn_bstems_kernel<8><<<grid, block, lds, st>>>(g, w, r); break;
-	case 16: cn_bstems_kernel<16><<<grid, block, lds, st>>>(g, w, r); break;
-	case 32: cn_bstems_kernel<32><<<grid, block, lds, st>>>(g, w, r); break;
-	case 64: cn_bstems_kernel<64><<<grid, block, lds, st>>>(g, w, r); break;
-	case 128: cn_bstems_kernel<128><<<grid, block, lds, st>>>(g, w, r); break;
-	case 256: cn_bstems_kernel<256><<<grid, block, lds, st>>>(g, w, r); break;
-	default: return hipErrorInvalidValue;
-	}
-	return hipGetLastError();
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_bstems_kernel<QQ>, (long long)r.B * g.M, 64, nbl_bstems_lds_bytes(g), st, g, w, r))
 }

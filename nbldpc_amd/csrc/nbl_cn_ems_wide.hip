@@ -1,72 +1,36 @@
 // nbldpc_amd/csrc/nbl_cn_ems_wide.hip -- EMS check node for checks of degree up to NBL_EMS_MAX_CHECK_DEGREE (nbl_create_ems_wide on a code
 // with a check above degree 8, or any such decoder under nbl_debug_force_generic(dec, 3)): the programme of nbl_cn_ems_wide_core.h, one
-// instantiation per q for every degree, under both schedules.  One check per workgroup of max(1, q / 64) waves.  The input formers are
-// those of cn_ems_kernel (nbl_kernels.hip: the v2c vectors of the variable-node pass) and cn_ems_layered_kernel (nbl_cn_layered.hip:
-// L_ch and the in-place c2v through the layer rows); the one-buffer argument of the layered schedule is unchanged -- the checks of a layer
-// share no variable, every input of a check is read before the workgroup's first barrier and every output written after it.
+// instantiation per q for every degree, under both schedules.  One check per workgroup of max(1, q / 64) waves.  The inputs are
+// EmsV2cInput (the v2c vectors of the variable-node pass) and EmsLayeredInput (L_ch and the in-place c2v through the layer rows) of
+// nbl_cn_shell.h; the one-buffer argument of the layered schedule is unchanged -- the checks of a layer share no variable, every
+// input of a check is read before the workgroup's first barrier and every output written after it.
 #include <hip/hip_runtime.h>
-#include "nbl_device.h"
-#include "nbl_kernels.h"
+#include "nbl_cn_shell.h"
 #include "nbl_cn_ems_wide_core.h"
 
 template <int Q>
 __global__ __launch_bounds__(EmsWide<Q>::NT) void cn_ems_wide_kernel(NblGraphDev g, NblWork w, NblRun r, int layers)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	const int b = nbl_codeword(w, r, blockIdx.x / g.M), m = blockIdx.x % g.M;
+	const int b = nbl_flooding_codeword(g, w, r);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
-	const double *V = w.v2c + (size_t)b * g.E * Q;
-	double *C = w.c2v + ((size_t)b * g.E + c0) * Q;
-	ems_wide_check_node<Q>(g, r, layers, smem, c0, dc, C, [&](int j) {
-		const double *Vj = V + (size_t)g.c_epos[c0 + j] * Q;
-		return [=](int a) { return Vj[a]; };
-	});
+	const NblCheck k = nbl_flooding_check(g, b);
+	const EmsV2cInput<Q> in = {w.v2c + (size_t)k.b * g.E * Q, g.c_epos, k.c0};
+	ems_wide_check_node<Q>(g, r, layers, smem, k.c0, k.dc, w.c2v + ((size_t)k.b * g.E + k.c0) * Q, in);
 }
 
-// the checks of one layer: grid = count * (codeword slots)
+// the checks of one layer
 template <int Q>
 __global__ __launch_bounds__(EmsWide<Q>::NT) void cn_ems_wide_layered_kernel(NblGraphDev g, NblWork w, NblRun r, NblLayerDev ly, int offset, int count, int layers)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	const int b = nbl_codeword(w, r, blockIdx.x / count), m = ly.chk[offset + blockIdx.x % count];
+	const int b = nbl_layer_codeword(w, r, count);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
-	const double *L = w.Lch + (size_t)b * g.N * Q;
-	double *Cb = w.c2v + (size_t)b * g.E * Q;
-	// input of edge j, variable n: P = L_ch[n], then + c2v of each of n's edges in n's order (the CURRENT values), then - c2v of this
-	// edge (include/nbldpc.h); the row gives every address after one index load
-	ems_wide_check_node<Q>(g, r, layers, smem, c0, dc, Cb + (size_t)c0 * Q, [&](int j) {
-		const int *row = ly.nbr + (size_t)(c0 + j) * NBL_LAYER_ROW;
-		const int dv = row[1];
-		const double *Ln = L + (size_t)row[0] * Q;
-		const double *own = Cb + (size_t)(c0 + j) * Q;
-		const double *nb[NBL_MAXDV];
-#pragma unroll
-		for (int d = 0; d < NBL_MAXDV; d++) nb[d] = Cb + (size_t)row[4 + (d < dv ? d : 0)] * Q;
-		return [=](int a) {
-			double P = Ln[a];
-#pragma unroll
-			for (int d = 0; d < NBL_MAXDV; d++)
-				if (d < dv) P = P + nb[d][a];
-			return P - own[a];
-		};
-	});
+	const NblCheck k = nbl_layer_check(g, ly, offset, count, b);
+	double *Cb = w.c2v + (size_t)k.b * g.E * Q;
+	const EmsLayeredInput<Q> in = {w.Lch + (size_t)k.b * g.N * Q, Cb, ly.nbr, k.c0};
+	ems_wide_check_node<Q>(g, r, layers, smem, k.c0, k.dc, Cb + (size_t)k.c0 * Q, in);
 }
-
-#define NBL_EMS_WIDE_Q(q, ...)                                  \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
 
 // [maxdc][q] inputs, prefix + ping + pong of [layers][q], one [q] output vector, the lists [maxdc][nm] (8 + 4 bytes an entry)
 size_t nbl_ems_wide_lds_bytes(int q, int maxdc, int nm, int nc)
@@ -77,34 +41,21 @@ size_t nbl_ems_wide_lds_bytes(int q, int maxdc, int nm, int nc)
 
 static bool wide_shape_ok(const NblGraphDev &g, const NblWork &w, const NblRun &r, size_t lds)
 {
-	return g.maxdc >= 2 && g.maxdc <= NBL_EMS_MAX_CHECK_DEGREE && r.nm >= 1 && r.nm <= g.q && r.nc >= 0 && lds <= NBL_EMS_WIDE_MAX_LDS && w.c2v;
+	return g.maxdc >= 2 && g.maxdc <= NBL_EMS_MAX_CHECK_DEGREE && r.nm >= 1 && r.nm <= g.q && r.nc >= 0 && lds <= NBL_MAX_LDS && w.c2v;
 }
 
 hipError_t nbl_launch_cn_ems_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st)
 {
 	const int layers = nbl_ems_layers(g.maxdc, r.nc);
 	const size_t lds = nbl_ems_wide_lds_bytes(g.q, g.maxdc, r.nm, r.nc);
-	const long long blocks = (long long)r.B * g.M;
-	if (!wide_shape_ok(g, w, r, lds) || !w.v2c || blocks > 0x7fffffffLL) return hipErrorInvalidValue; // (nbl_create_ems_wide refuses such shapes)
-	dim3 grid((unsigned)blocks);
-	NBL_EMS_WIDE_Q(g.q, {
-		if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)cn_ems_wide_kernel<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		cn_ems_wide_kernel<QQ><<<grid, dim3(EmsWide<QQ>::NT), lds, st>>>(g, w, r, layers);
-	})
-	return hipGetLastError();
+	if (!wide_shape_ok(g, w, r, lds) || !w.v2c) return hipErrorInvalidValue; // (nbl_create_ems_wide refuses such shapes)
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_ems_wide_kernel<QQ>, (long long)r.B * g.M, EmsWide<QQ>::NT, lds, st, g, w, r, layers))
 }
 
 hipError_t nbl_launch_cn_ems_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st)
 {
 	const int layers = nbl_ems_layers(g.maxdc, r.nc);
 	const size_t lds = nbl_ems_wide_lds_bytes(g.q, g.maxdc, r.nm, r.nc);
-	const long long blocks = (long long)r.B * count;
-	if (count < 1 || offset < 0 || offset + count > g.M || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-	if (!wide_shape_ok(g, w, r, lds)) return hipErrorInvalidValue;
-	dim3 grid((unsigned)blocks);
-	NBL_EMS_WIDE_Q(g.q, {
-		if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)cn_ems_wide_layered_kernel<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		cn_ems_wide_layered_kernel<QQ><<<grid, dim3(EmsWide<QQ>::NT), lds, st>>>(g, w, r, ly, offset, count, layers);
-	})
-	return hipGetLastError();
+	if (!nbl_layer_range_ok(g, offset, count) || !wide_shape_ok(g, w, r, lds)) return hipErrorInvalidValue;
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_ems_wide_layered_kernel<QQ>, (long long)r.B * count, EmsWide<QQ>::NT, lds, st, g, w, r, ly, offset, count, layers))
 }

@@ -6,8 +6,7 @@
 // (nbl_cn_ems_core.h: the same device code) and writes its c2v vectors back into the same buffer.  The checks of a layer share no
 // variable, so no wave of a launch reads what another wave of that launch writes; the launches of one stream order the layers.
 #include <hip/hip_runtime.h>
-#include "nbl_device.h"
-#include "nbl_kernels.h"
+#include "nbl_cn_shell.h"
 #include "nbl_cn_ems_core.h"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -61,49 +60,19 @@ template <int Q>
 __global__ __launch_bounds__(64) void cn_ems_layered_kernel(NblGraphDev g, NblWork w, NblRun r, NblLayerDev ly, int offset, int count, int layers)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	const int b = nbl_codeword(w, r, blockIdx.x / count), m = ly.chk[offset + blockIdx.x % count];
+	const int b = nbl_layer_codeword(w, r, count);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
-	const double *L = w.Lch + (size_t)b * g.N * Q;
-	double *Cb = w.c2v + (size_t)b * g.E * Q;
-	// input of edge j, variable n: P = L_ch[n], then + c2v of each of n's edges in n's order (the CURRENT values), then - c2v of this
-	// edge (include/nbldpc.h); the row gives every address after one index load
-	ems_check_node<Q>(g, w, r, layers, smem, c0, dc, Cb + (size_t)c0 * Q, [&](int j) {
-		const int *row = ly.nbr + (size_t)(c0 + j) * NBL_LAYER_ROW;
-		const int dv = row[1];
-		const double *Ln = L + (size_t)row[0] * Q;
-		const double *own = Cb + (size_t)(c0 + j) * Q;
-		const double *nb[NBL_MAXDV];
-#pragma unroll
-		for (int d = 0; d < NBL_MAXDV; d++) nb[d] = Cb + (size_t)row[4 + (d < dv ? d : 0)] * Q;
-		return [=](int a) {
-			double P = Ln[a];
-#pragma unroll
-			for (int d = 0; d < NBL_MAXDV; d++)
-				if (d < dv) P = P + nb[d][a];
-			return P - own[a];
-		};
-	});
+	const NblCheck k = nbl_layer_check(g, ly, offset, count, b);
+	double *Cb = w.c2v + (size_t)k.b * g.E * Q;
+	const EmsLayeredInput<Q> in = {w.Lch + (size_t)k.b * g.N * Q, Cb, ly.nbr, k.c0}; // (nbl_cn_shell.h)
+	ems_check_node<Q>(g, w, r, layers, smem, k.c0, k.dc, Cb + (size_t)k.c0 * Q, in);
 }
-
-#define NBL_LAYERED_Q(q, ...)                                   \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
 
 hipError_t nbl_launch_vn_decide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st)
 {
 	const long long nodes = (long long)r.B * g.N;
 	dim3 grid((unsigned)((nodes + 3) / 4)), block(256);
-	NBL_LAYERED_Q(g.q, vn_decide_kernel<QQ><<<grid, block, 0, st>>>(g, w, r))
+	NBL_DISPATCH_Q(g.q, vn_decide_kernel<QQ><<<grid, block, 0, st>>>(g, w, r))
 	return hipGetLastError();
 }
 
@@ -111,13 +80,6 @@ hipError_t nbl_launch_cn_ems_layered(const NblGraphDev &g, const NblWork &w, con
 {
 	const int layers = nbl_ems_layers(g.maxdc, r.nc);
 	const size_t lds = nbl_ems_lds_bytes(g.q, g.maxdc, r.nm, r.nc);
-	const long long blocks = (long long)r.B * count;
-	if (count < 1 || offset < 0 || offset + count > g.M || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-	if (lds > 160 * 1024) return hipErrorInvalidValue; // (nbl_create_layered refuses such shapes)
-	dim3 grid((unsigned)blocks), block(64);
-	NBL_LAYERED_Q(g.q, {
-		if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)cn_ems_layered_kernel<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		cn_ems_layered_kernel<QQ><<<grid, block, lds, st>>>(g, w, r, ly, offset, count, layers);
-	})
-	return hipGetLastError();
+	if (!nbl_layer_range_ok(g, offset, count) || lds > NBL_MAX_LDS) return hipErrorInvalidValue; // (nbl_create_layered refuses such shapes)
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_ems_layered_kernel<QQ>, (long long)r.B * count, 64, lds, st, g, w, r, ly, offset, count, layers))
 }

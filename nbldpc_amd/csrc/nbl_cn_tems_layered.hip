@@ -4,8 +4,9 @@
 // One iteration is: vn_decide_kernel and syn_kernel (as for layered EMS), then ONE launch of cn_tems_layered_kernel per layer.  A
 // check of layer l forms the raw input of each of its edges from L_ch and the c2v buffer as the layers before it left it, damps it
 // against the edge's stored v2c vector (the reference's per-edge damping, NBLDPC.cpp:1029-1052: where the hard decisions of the two
-// differ, 0.25 old + 0.75 new), stores the result back as the edge's v2c, runs the T-EMS check-node programme of the general kernels
-// (nbl_cn_tems_core.h: the same device code) on it and writes its c2v vectors back into the same buffer.
+// differ, 0.25 old + 0.75 new), stores the result back as the edge's v2c (BpLayeredInput, nbl_cn_bp_inputs.h), runs the T-EMS
+// check-node programme of the general kernels (nbl_cn_tems_core.h: the same device code) on it and writes its c2v vectors back into
+// the same buffer.
 //
 // What makes one c2v and one v2c buffer enough:
 //   * every global read of a check's inputs (L_ch, the neighbours' c2v, its own c2v, its stored v2c) happens in step 1 of the
@@ -14,67 +15,22 @@
 //   * an edge belongs to one check, so its v2c vector is read and written by that check's wave alone;
 //   * the launches of one stream order the layers.
 #include <hip/hip_runtime.h>
-#include "nbl_device.h"
-#include "nbl_kernels.h"
+#include "nbl_cn_shell.h"
 #include "nbl_cn_tems_core.h"
+#include "nbl_cn_bp_inputs.h"
 
-// the checks of one layer: one wave per (codeword, check); grid = count * (codeword slots)
+// the checks of one layer: one wave per (codeword, check)
 template <int Q, bool FAST>
 __global__ __launch_bounds__(64) void cn_tems_layered_kernel(NblGraphDev g, NblWork w, NblRun r, NblLayerDev ly, int offset, int count)
 {
-	constexpr int NS = Fld<Q>::NS;
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	const int lane = lane_id();
-	const int b = nbl_codeword(w, r, blockIdx.x / count), m = ly.chk[offset + blockIdx.x % count];
+	const int b = nbl_layer_codeword(w, r, count);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
-	const double *L = w.Lch + (size_t)b * g.N * Q;
-	double *Cb = w.c2v + (size_t)b * g.E * Q;
-	double *Vb = w.v2c + (size_t)b * g.E * Q;
-	// input of edge j, variable n: P = L_ch[n], then + c2v of each of n's edges in n's order (the CURRENT values); raw = P - c2v of this
-	// edge; damped against the stored v2c of this edge where the two decide differently; stored back (include/nbldpc.h)
-	auto input = [&](int j, double (&v)[NS]) {
-		const int *row = ly.nbr + (size_t)(c0 + j) * NBL_LAYER_ROW;
-		const int dv = row[1];
-		const double *Ln = L + (size_t)row[0] * Q;
-		const double *own = Cb + (size_t)(c0 + j) * Q;
-		double *Vd = Vb + (size_t)g.c_epos[c0 + j] * Q;
-		double ov[NS];
-#pragma unroll
-		for (int i = 0; i < NS; i++) {
-			int a = lane + 64 * i;
-			v[i] = (a < Q) ? Ln[a] : 0.0;
-			ov[i] = (a < Q) ? Vd[a] : 0.0;
-		}
-		for (int d = 0; d < dv; d++) {
-			const double *Cd = Cb + (size_t)row[4 + d] * Q;
-#pragma unroll
-			for (int i = 0; i < NS; i++) {
-				int a = lane + 64 * i;
-				if (a < Q) v[i] = v[i] + Cd[a];
-			}
-		}
-#pragma unroll
-		for (int i = 0; i < NS; i++) {
-			int a = lane + 64 * i;
-			if (a < Q) v[i] = v[i] - own[a];
-		}
-		const int before = wave_decide<NS>(ov, lane, Q);
-		const int after = wave_decide<NS>(v, lane, Q);
-		if (before != after) {
-#pragma unroll
-			for (int i = 0; i < NS; i++) v[i] = __dadd_rn(__dmul_rn(r.damp_old, ov[i]), __dmul_rn(r.damp_new, v[i]));
-		}
-#pragma unroll
-		for (int i = 0; i < NS; i++) {
-			int a = lane + 64 * i;
-			if (a == 0) v[i] = 0.0;
-			if (a < Q) Vd[a] = v[i];
-		}
-	};
-	if (FAST) tems_fast_check_node<Q>(g, r, smem, c0, dc, Cb + (size_t)c0 * Q, input);
-	else tems_check_node<Q>(g, r, smem, c0, dc, Cb + (size_t)c0 * Q, input);
+	const NblCheck k = nbl_layer_check(g, ly, offset, count, b);
+	double *Cb = w.c2v + (size_t)k.b * g.E * Q;
+	const BpLayeredInput<Q> input = {w.Lch + (size_t)k.b * g.N * Q, Cb, w.v2c + (size_t)k.b * g.E * Q, ly.nbr, g.c_epos, k.c0, lane_id(), r.damp_old, r.damp_new};
+	if (FAST) tems_fast_check_node<Q>(g, r, smem, k.c0, k.dc, Cb + (size_t)k.c0 * Q, input);
+	else tems_check_node<Q>(g, r, smem, k.c0, k.dc, Cb + (size_t)k.c0 * Q, input);
 }
 
 size_t nbl_tems_layered_lds_bytes(int q, int maxdc, int nc)
@@ -84,38 +40,14 @@ size_t nbl_tems_layered_lds_bytes(int q, int maxdc, int nc)
 	return gen > fast ? gen : fast;
 }
 
-#define NBL_LAYERED_Q(q, ...)                                   \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
-
 hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st)
 {
 	const bool fast = nbl_tems_use_fast(r.nc);
 	const size_t lds = fast ? nbl_tems_fast_lds_bytes(g.q, g.maxdc) : nbl_tems_lds_bytes(g.q, g.maxdc, r.nc);
-	const long long blocks = (long long)r.B * count;
-	if (count < 1 || offset < 0 || offset + count > g.M || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-	if (lds > 160 * 1024) return hipErrorInvalidValue; // (nbl_create_layered_ex refuses such shapes)
+	if (!nbl_layer_range_ok(g, offset, count) || lds > NBL_MAX_LDS) return hipErrorInvalidValue; // (nbl_create_layered_ex refuses such shapes)
 	if ((double)g.p * g.maxdc > 32.0) return hipErrorInvalidValue; // path code must fit 32 bits (refused at creation)
 	if (!w.v2c) return hipErrorInvalidValue;
-	dim3 grid((unsigned)blocks), block(64);
-	if (fast) {
-		NBL_LAYERED_Q(g.q, {
-			if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)cn_tems_layered_kernel<QQ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			cn_tems_layered_kernel<QQ, true><<<grid, block, lds, st>>>(g, w, r, ly, offset, count);
-		})
-	} else {
-		NBL_LAYERED_Q(g.q, {
-			if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)cn_tems_layered_kernel<QQ, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			cn_tems_layered_kernel<QQ, false><<<grid, block, lds, st>>>(g, w, r, ly, offset, count);
-		})
-	}
-	return hipGetLastError();
+	const long long blocks = (long long)r.B * count;
+	if (fast) { NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_tems_layered_kernel<QQ, true>, blocks, 64, lds, st, g, w, r, ly, offset, count)) }
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_tems_layered_kernel<QQ, false>, blocks, 64, lds, st, g, w, r, ly, offset, count))
 }

@@ -274,6 +274,48 @@ template <int NS> __device__ __forceinline__ int wave_decide_keyed(const double 
 	return arg; // (mx > 0 here)
 }
 
+// ---- the same on floats (single-precision FHT decoding), one register per value ----
+// v_max_f32 without the canonicalising pre-max hipcc adds in front of fmaxf() on loaded values
+__device__ __forceinline__ float fmax32(float a, float b)
+{
+	float r;
+	asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+	return r;
+}
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_f32(float v)
+{
+	return __int_as_float(dpp_i32<CTRL, ROW_MASK>(__float_as_int(v)));
+}
+__device__ __forceinline__ float read_lane_f32(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
+__device__ __forceinline__ float wave_fmax32(float v)
+{
+	v = fmax32(v, dpp_f32<0x111, 0xF>(v));
+	v = fmax32(v, dpp_f32<0x112, 0xF>(v));
+	v = fmax32(v, dpp_f32<0x114, 0xF>(v));
+	v = fmax32(v, dpp_f32<0x118, 0xF>(v));
+	v = fmax32(v, dpp_f32<0x142, 0xA>(v));
+	v = fmax32(v, dpp_f32<0x143, 0xC>(v));
+	return read_lane_f32(v, 63);
+}
+// DecideLLRVector on a float vector: wave_decide with the same tie rule (running maximum starts at 0, strict '>': the lowest symbol
+// wins ties, a vector without a positive entry decides 0).  Slot a = 0 must hold a value <= 0.
+template <int NS> __device__ __forceinline__ int wave_decide32(const float (&v)[NS], int lane, int q)
+{
+	float best = 0.0f;
+#pragma unroll
+	for (int i = 0; i < NS; i++)
+		if (lane + 64 * i < q) best = fmax32(best, v[i]);
+	if (!__ballot(best > 0.0f)) return 0;
+	const float mx = wave_fmax32(best);
+	int arg = 0;
+#pragma unroll
+	for (int i = NS - 1; i >= 0; i--) {
+		const uint64_t hit = __ballot(lane + 64 * i < q && v[i] == mx);
+		arg = hit ? 64 * i + __builtin_ctzll(hit) : arg;
+	}
+	return arg;
+}
+
 // check-to-variable shaping, NBLDPC.cpp:903-916 / 1113-1126
 __device__ __forceinline__ double shape_llr(double y, double factor, double offset)
 {

@@ -112,18 +112,6 @@ __global__ void widen32_kernel(const float *__restrict__ src, double *__restrict
 	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] = (double)src[i];
 }
 
-#define NBL_FHT32_Q(q, ...)                                     \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
-
 hipError_t nbl_launch_narrow32(const NblGraphDev &g, const double *d_Lch, const NblWork32 &f, int B, hipStream_t st)
 {
 	const long long nodes = (long long)B * g.N, blocks = (nodes + 3) / 4;
@@ -137,8 +125,8 @@ hipError_t nbl_launch_vn32(const NblGraphDev &g, const NblWork &w, const NblWork
 	const long long nodes = (long long)r.B * g.N, blocks = (nodes + 3) / 4;
 	if (blocks > 0x7fffffffLL || !f.Lf || !f.c2v || (write_v2c && !f.v2c)) return hipErrorInvalidValue;
 	dim3 grid((unsigned)blocks), block(256);
-	if (write_v2c) { NBL_FHT32_Q(g.q, vn32_kernel<QQ, true><<<grid, block, 0, st>>>(g, w, f, r)) }
-	else { NBL_FHT32_Q(g.q, vn32_kernel<QQ, false><<<grid, block, 0, st>>>(g, w, f, r)) }
+	if (write_v2c) { NBL_DISPATCH_Q(g.q, vn32_kernel<QQ, true><<<grid, block, 0, st>>>(g, w, f, r)) }
+	else { NBL_DISPATCH_Q(g.q, vn32_kernel<QQ, false><<<grid, block, 0, st>>>(g, w, f, r)) }
 	return hipGetLastError();
 }
 

@@ -4,6 +4,24 @@
 #include "nbl_common.h"
 #include "nbl_plan.h" // the nbl_*_applicable predicates, defined beside their kernels
 
+// dynamic LDS of one workgroup on gfx950: what a kernel gets without opting in, and the ceiling every creation entry refuses above
+// (pure arithmetic, before the device); the launch helper of nbl_cn_shell.h opts in between the two
+#define NBL_LDS_OPT_IN (64 * 1024)
+#define NBL_MAX_LDS (160 * 1024)
+
+// inside a launcher: the statement(s) once per field size, with QQ = q as a constant; any other q returns hipErrorInvalidValue
+#define NBL_DISPATCH_Q(q, ...)                                  \
+	switch (q) {                                                \
+	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
+	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
+	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
+	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
+	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
+	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
+	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
+	default: return hipErrorInvalidValue;                       \
+	}
+
 hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblWork &w, int B, int write_v2c, hipStream_t st);
 hipError_t nbl_launch_demod(const double *d_rx, int L, double sigma, int mod_order, const double *d_cons, const int *d_src,
                             const NblGraphDev &g, const NblWork &w, int B, hipStream_t st,
@@ -18,7 +36,7 @@ hipError_t nbl_launch_syn(const NblGraphDev &g, const NblWork &w, const NblRun &
 hipError_t nbl_launch_compact(const uint8_t *done, int B, int *active, int *n_act, hipStream_t st);
 hipError_t nbl_launch_cn_ems(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_unpad(const double *src, double *dst, const int *map, int rows, int q, hipStream_t st);
-// general EMS kernel: deviation-count layers, and the bytes of LDS of one check (pure arithmetic: nbl_create refuses above 160 KB)
+// general EMS kernel: deviation-count layers, and the bytes of LDS of one check (pure arithmetic: nbl_create refuses above NBL_MAX_LDS)
 int nbl_ems_layers(int maxdc, int nc);
 size_t nbl_ems_lds_bytes(int q, int maxdc, int nm, int nc);
 
@@ -29,7 +47,7 @@ hipError_t nbl_launch_cn_ems_layered(const NblGraphDev &g, const NblWork &w, con
 
 // damped layered schedule for T-EMS (nbl_cn_tems_layered.hip): the checks of one layer; each forms its inputs from L_ch and the in-place
 // c2v, damps them against the edge's stored v2c (w.v2c, updated in place) and runs the programme of nbl_cn_tems_core.h.  LDS: the
-// larger of the two programmes a launch may take (pure arithmetic: nbl_create_layered_ex refuses above 160 KB before the device)
+// larger of the two programmes a launch may take (pure arithmetic: nbl_create_layered_ex refuses above NBL_MAX_LDS before the device)
 size_t nbl_tems_layered_lds_bytes(int q, int maxdc, int nc);
 hipError_t nbl_launch_cn_tems_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
@@ -65,8 +83,7 @@ hipError_t nbl_launch_widen32(const float *src, double *dst, long long n, hipStr
 
 // EMS check node for checks up to degree NBL_EMS_MAX_CHECK_DEGREE (nbl_create_ems_wide; nbl_cn_ems_wide.hip): the programme of
 // nbl_cn_ems_wide_core.h, one check per workgroup of max(1, q / 64) waves, flooding and the checks of one layer.  The bytes of LDS of one
-// workgroup are pure arithmetic: nbl_create_ems_wide refuses above NBL_EMS_WIDE_MAX_LDS before the device, both launchers size by it
-#define NBL_EMS_WIDE_MAX_LDS (160 * 1024)
+// workgroup are pure arithmetic: nbl_create_ems_wide refuses above NBL_MAX_LDS before the device, both launchers size by it
 size_t nbl_ems_wide_lds_bytes(int q, int maxdc, int nm, int nc);
 hipError_t nbl_launch_cn_ems_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_ems_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
@@ -74,17 +91,15 @@ hipError_t nbl_launch_cn_ems_wide_layered(const NblGraphDev &g, const NblWork &w
 // T-EMS check node for checks up to degree NBL_TEMS_MAX_CHECK_DEGREE over any field (nbl_create_tems_wide; nbl_cn_tems_wide.hip): the
 // programme of nbl_cn_tems_wide_core.h, one check per workgroup of max(1, q / 64) waves, at most NBL_TEMS_WIDE_MAX_NC (nbl_tems_path.h)
 // deviations per path, flooding and the checks of one layer.  The bytes of LDS of one workgroup are pure arithmetic:
-// nbl_create_tems_wide refuses above NBL_TEMS_WIDE_MAX_LDS before the device, both launchers size by it
-#define NBL_TEMS_WIDE_MAX_LDS (160 * 1024)
+// nbl_create_tems_wide refuses above NBL_MAX_LDS before the device, both launchers size by it
 size_t nbl_tems_wide_lds_bytes(int q, int maxdc, int nr, int nc);
 hipError_t nbl_launch_cn_tems_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_tems_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
 
 // exact log-QSPA check node for checks up to degree NBL_BP_MAX_CHECK_DEGREE (nbl_create_bp_wide; nbl_cn_bp_wide.hip): the programme of
 // nbl_cn_bp_wide_core.h, one check per workgroup of max(1, q / 64) waves, flooding and the checks of one layer.  LDS of one workgroup:
-// (maxdc + 5) q 8 + 256 bytes, at most 76,032 B (q = 256, degree 32) -- below NBL_BP_WIDE_MAX_LDS for every shape the ABI accepts, so
+// (maxdc + 5) q 8 + 256 bytes, at most 76,032 B (q = 256, degree 32) -- below NBL_MAX_LDS for every shape the ABI accepts, so
 // nbl_create_bp_wide refuses no shape for LDS; both launchers size by the one function and check the bound all the same
-#define NBL_BP_WIDE_MAX_LDS (160 * 1024)
 size_t nbl_bp_wide_lds_bytes(int q, int maxdc);
 hipError_t nbl_launch_cn_bp_wide(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_bp_wide_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);
@@ -92,9 +107,8 @@ hipError_t nbl_launch_cn_bp_wide_layered(const NblGraphDev &g, const NblWork &w,
 // Min-Max check node (method 3; nbl_create_minmax; nbl_cn_minmax.hip): the programme of nbl_cn_minmax_core.h, one check per workgroup of
 // max(1, q / 64) waves, check degrees up to NBL_MINMAX_MAX_CHECK_DEGREE, flooding (inputs: w.v2c) and the checks of one layer (inputs:
 // L_ch and the in-place c2v).  LDS of one workgroup: (maxdc + 4) q 8 bytes, at most 73,728 B (q = 256, degree 32) -- below
-// NBL_MINMAX_MAX_LDS for every shape the ABI accepts, so nbl_create_minmax refuses no shape for LDS; both launchers size by the one
+// NBL_MAX_LDS for every shape the ABI accepts, so nbl_create_minmax refuses no shape for LDS; both launchers size by the one
 // function and check the bound all the same
-#define NBL_MINMAX_MAX_LDS (160 * 1024)
 size_t nbl_minmax_lds_bytes(int q, int maxdc);
 hipError_t nbl_launch_cn_minmax(const NblGraphDev &g, const NblWork &w, const NblRun &r, hipStream_t st);
 hipError_t nbl_launch_cn_minmax_layered(const NblGraphDev &g, const NblWork &w, const NblRun &r, const NblLayerDev &ly, int offset, int count, hipStream_t st);

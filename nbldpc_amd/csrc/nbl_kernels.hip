@@ -7,8 +7,7 @@
 // Everything is FP64 and every floating-point expression keeps the reference's association order; the file
 // is compiled with -ffp-contract=off so no multiply-add is fused.
 #include <hip/hip_runtime.h>
-#include "nbl_device.h"
-#include "nbl_kernels.h"
+#include "nbl_cn_shell.h"
 #include "nbl_cn_ems_core.h"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -329,16 +328,11 @@ template <int Q>
 __global__ __launch_bounds__(64) void cn_ems_kernel(NblGraphDev g, NblWork w, NblRun r, int layers)
 {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
-	const int b = nbl_codeword(w, r, blockIdx.x / g.M), m = blockIdx.x % g.M;
+	const int b = nbl_flooding_codeword(g, w, r);
 	if (b < 0) return;
-	if (!r.fixed_iters && w.done[b]) return;
-	const int c0 = g.coff[m], dc = g.coff[m + 1] - c0;
-	const double *V = w.v2c + (size_t)b * g.E * Q;
-	double *C = w.c2v + ((size_t)b * g.E + c0) * Q;
-	ems_check_node<Q>(g, w, r, layers, smem, c0, dc, C, [&](int j) {
-		const double *Vj = V + (size_t)g.c_epos[c0 + j] * Q;
-		return [=](int a) { return Vj[a]; };
-	});
+	const NblCheck k = nbl_flooding_check(g, b);
+	const EmsV2cInput<Q> in = {w.v2c + (size_t)k.b * g.E * Q, g.c_epos, k.c0}; // (nbl_cn_shell.h)
+	ems_check_node<Q>(g, w, r, layers, smem, k.c0, k.dc, w.c2v + ((size_t)k.b * g.E + k.c0) * Q, in);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -359,18 +353,6 @@ __global__ void unpad_kernel(const double *__restrict__ src, double *__restrict_
 // ---------------------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------------------
-#define NBL_DISPATCH_Q(q, ...)                                  \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
-
 hipError_t nbl_launch_init(const double *d_Lin, const NblGraphDev &g, const NblWork &w, int B, int write_v2c, hipStream_t st)
 {
 	if (d_Lin && g.q >= 64 && B > 0) {
@@ -491,13 +473,8 @@ hipError_t nbl_launch_cn_ems(const NblGraphDev &g, const NblWork &w, const NblRu
 {
 	const int layers = nbl_ems_layers(g.maxdc, r.nc);
 	const size_t lds = nbl_ems_lds_bytes(g.q, g.maxdc, r.nm, r.nc);
-	dim3 grid((unsigned)((long long)r.B * g.M)), block(64);
-	if (lds > 160 * 1024) return hipErrorInvalidValue; // (nbl_create refuses such shapes)
-	NBL_DISPATCH_Q(g.q, {
-		if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)cn_ems_kernel<QQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		cn_ems_kernel<QQ><<<grid, block, lds, st>>>(g, w, r, layers);
-	})
-	return hipGetLastError();
+	if (lds > NBL_MAX_LDS) return hipErrorInvalidValue; // (nbl_create refuses such shapes)
+	NBL_DISPATCH_Q(g.q, return nbl_launch_checks(cn_ems_kernel<QQ>, (long long)r.B * g.M, 64, lds, st, g, w, r, layers))
 }
 
 hipError_t nbl_launch_unpad(const double *src, double *dst, const int *map, int rows, int q, hipStream_t st)

@@ -25,7 +25,7 @@ struct NblPlan {
 	bool want_v2c; // v2c exists in HBM: something reads it (the unfused path, the damped methods, state read-back)
 	bool f32;      // nbl_create_fht32 / nbl_create_fht32_wide: cn (fht, fht_layered, fht_wide or fht_wide_layered) is run by its binary32
 	               // instance on the float message state; named fht32 / fht32_layered / fht32_wide / fht32_wide_layered
-	bool minmax;   // nbl_create_minmax: cn (ems_wide or ems_wide_layered: the launch shape, the input formers and the buffers are those) is run
+	bool minmax;   // nbl_create_minmax: cn (ems_wide or ems_wide_layered: the launch shape, the input formers of nbl_cn_shell.h and the buffers are those) is run
 	               // by the Min-Max programme (nbl_cn_minmax.hip); named minmax / minmax_layered.  A flag beside cn, as f32 is: NblCn lists
 	               // the kernels tests/test_idd_kinds.py wants a loop cell for, and Min-Max pins its loop in tests/test_gpu_minmax.py
 };

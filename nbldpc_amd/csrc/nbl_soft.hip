@@ -152,18 +152,6 @@ __global__ __launch_bounds__(256) void soft_output_kernel(NblGraphDev g, const d
 	if (lane < P) bit_llr[((size_t)b * g.N + n) * P + lane] = mine;
 }
 
-#define NBL_SOFT_Q(q, ...)                                      \
-	switch (q) {                                                \
-	case 4: { constexpr int QQ = 4; __VA_ARGS__; } break;       \
-	case 8: { constexpr int QQ = 8; __VA_ARGS__; } break;       \
-	case 16: { constexpr int QQ = 16; __VA_ARGS__; } break;     \
-	case 32: { constexpr int QQ = 32; __VA_ARGS__; } break;     \
-	case 64: { constexpr int QQ = 64; __VA_ARGS__; } break;     \
-	case 128: { constexpr int QQ = 128; __VA_ARGS__; } break;   \
-	case 256: { constexpr int QQ = 256; __VA_ARGS__; } break;   \
-	default: return hipErrorInvalidValue;                       \
-	}
-
 hipError_t nbl_launch_soft_output(const NblGraphDev &g, const double *d_Lch, const NblSoftSrc &src, int B, int metric, double *d_sym_llr,
                                   double *d_bit_llr, hipStream_t st, bool extrinsic)
 {
@@ -171,9 +159,9 @@ hipError_t nbl_launch_soft_output(const NblGraphDev &g, const double *d_Lch, con
 	if (B < 1 || blocks > 0x7fffffffLL || !src.last || (src.per_codeword && (!src.bufA || !src.bufB || !src.done || !src.iters))) return hipErrorInvalidValue;
 	dim3 grid((unsigned)blocks), block(256);
 	if (extrinsic) {
-		NBL_SOFT_Q(g.q, soft_output_kernel<QQ, true><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
+		NBL_DISPATCH_Q(g.q, soft_output_kernel<QQ, true><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
 	} else {
-		NBL_SOFT_Q(g.q, soft_output_kernel<QQ><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
+		NBL_DISPATCH_Q(g.q, soft_output_kernel<QQ><<<grid, block, 0, st>>>(g, d_Lch, src, B, metric, d_sym_llr, d_bit_llr))
 	}
 	return hipGetLastError();
 }
